@@ -25,7 +25,14 @@ candidate: cache blocks with plain launches, cache blocks with the inner loop as
 the host's launch rate is close to the GPU's pace, all chains per launch), the fastest candidate
 is THE timed region; the others are measured afterwards for the roofline object.
 
-JSON extras (contract in the task statement):
+A plain run (``python bench.py --gpus 1 --steps K --warmup W``) sets up, warms up (the scheduling autotune
+included), times the K steps and prints the result line; ``--dump-outputs DIR`` adds what the timed call returned
+in its last step as ``DIR/<name>.npy`` (see ``write_outputs``).  Every other measurement or check of this file
+(launch-timed rooflines, the user-callable and ESS regions, parity against the oracle, the CPU baseline, the
+jax.random pin, the C3 / C5 / C4 sub-objects of the default run, the extra regions of ``--config c3/c4/c5``)
+runs only with ``--full``.
+
+JSON extras (``--full``; contract in the task statement):
   roofline      dominant kernel = fused kick+drift leapfrog, ALGORITHMIC bytes per launch
                 (20 B x D x chains per launch: read p,g,q; write p,q) / mean launch duration measured
                 with HIP events on the launch stream inside a timed region.  ``frac`` is the
@@ -373,7 +380,7 @@ def compact_line(out, full_path):
     c = _pick(out, "metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "mean_acceptance", "end_to_end_frac_of_28B_roofline", "ranks",
               "backend", "per_rank_ms_per_step", "devices_distinct", "n_gpus_note")
-    if "roofline" in out:
+    if isinstance(out.get("roofline"), dict):
         c["roofline"] = _pick(out["roofline"], *_ROOF_KEYS)
         ts = out["roofline"].get("traffic_source")
         if ts:
@@ -384,7 +391,7 @@ def compact_line(out, full_path):
             c["cpu_baseline"]["sample"] = c["cpu_baseline"]["sample"][:180]
         if isinstance(c["cpu_baseline"].get("jax_baseline"), str):
             c["cpu_baseline"]["jax_baseline"] = c["cpu_baseline"]["jax_baseline"][:80]
-    if "parity" in out:
+    if isinstance(out.get("parity"), dict):
         c["parity"] = _pick(out["parity"], *_PARITY_KEYS)
     if isinstance(out.get("ess"), dict):
         c["ess_per_sec_contract_params"] = out["ess"].get("min_ess_per_sec_all_chains")
@@ -442,6 +449,60 @@ def write_full_record(out):
         print(f"bench.py: could not write {path}: {e!r}", file=sys.stderr)
         path = "stderr"
     return path
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_SAMPLED_BYTES = 48 << 20  # what the chain-sampled arrays may take together
+DUMP_WHOLE_BYTES = 1 << 20  # arrays up to this size are written whole
+
+
+def _dump_leaves(x, name):
+    """(name, tensor or number) for every array of a returned structure: NamedTuple fields, dict keys and tuple
+    indices joined with '.'; None and other objects are skipped."""
+    if isinstance(x, torch.Tensor):
+        yield name, x
+    elif isinstance(x, (bool, int, float)):
+        yield name, torch.tensor(float(x), dtype=torch.float64)
+    elif hasattr(x, "_fields"):
+        for f in x._fields:
+            yield from _dump_leaves(getattr(x, f), f"{name}.{f}" if name else f)
+    elif isinstance(x, dict):
+        for k in sorted(x):
+            yield from _dump_leaves(x[k], f"{name}.{k}" if name else str(k))
+    elif isinstance(x, (list, tuple)):
+        for i, v in enumerate(x):
+            yield from _dump_leaves(v, f"{name}.{i}" if name else str(i))
+
+
+def write_outputs(out_dir, returned, n_chains):
+    """``--dump-outputs``: every array of ``returned`` (what the timed call handed its caller in the last timed step)
+    as ``out_dir/<name>.npy`` -- float32 stays float32; float64, integer and boolean arrays are written as float64.
+    Arrays larger than 1 MiB with a chain axis keep a fixed sample of chains (seed 0, drawn from the chain count alone,
+    so two builds write the same chains; listed in ``chain_sample.npy``), sized so that they take at most 48 MiB
+    together.  The whole dump is at most 64 MB."""
+    leaves = []
+    for name, t in _dump_leaves(returned, ""):
+        t = t.detach()
+        t = t.float() if t.dtype in (torch.float16, torch.bfloat16, torch.float32) else t.double()
+        axis = next((a for a, s in enumerate(t.shape) if s == n_chains), None)
+        leaves.append((name, t, axis if t.numel() * t.element_size() > DUMP_WHOLE_BYTES else None))
+    per_chain = sum(t.numel() * t.element_size() // n_chains for _, t, a in leaves if a is not None)
+    k = min(n_chains, max(1, DUMP_SAMPLED_BYTES // max(per_chain, 1)))
+    arrays = {}
+    if k < n_chains:
+        idx = np.sort(np.random.default_rng(0).permutation(n_chains)[:k])
+        arrays["chain_sample"] = idx.astype(np.float64)
+    for name, t, axis in leaves:
+        if axis is not None and k < n_chains:
+            t = t.index_select(axis, torch.as_tensor(idx, device=t.device))
+        arrays[name] = t.cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES} "
+                         f"({', '.join(f'{n} {a.shape}' for n, a in arrays.items())})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 
@@ -616,11 +677,12 @@ def bench_c2(args, ctx):
     n_sub = min(1024, N)
     timed_kernel = "bjx_leapfrog_diag"
 
-    def measure(chain_block, use_graph, collect_draws, steps=None, fn=None, eps=None, timing=True, streams=1):
+    def measure(chain_block, use_graph, collect_draws, steps=None, fn=None, eps=None, timing=True, streams=1,
+                dump=False):
         """W warm-up + K timed transitions in one scheduling mode.  The warm-up runs EXACTLY the
         timed loop's body (bookkeeping torch ops and launch-timer events included) plus one priming
         pass: on a fresh box the first use of any kernel pages its code object in from disk, which
-        must not land in the timed region."""
+        must not land in the timed region.  ``dump``: the region whose last step --dump-outputs writes."""
         steps = args.steps if steps is None else steps
         alg = bjx.hmc(target if fn is None else fn, args.eps if eps is None else eps, imm, L,
                       chain_offset=rank * N, chain_block=chain_block, use_graph=use_graph,
@@ -631,7 +693,8 @@ def bench_c2(args, ctx):
         # queue around the launch; at ~50 us launches, bracketing every 4th one slowed the whole
         # timed region by 13 %, so short launches are sampled sparsely.
         every = args.time_every or (16 if launches >= 100 else 1)
-        timing = timing and not args.no_launch_timing and not use_graph  # no events inside a graph
+        # no events inside a graph; the launch timings feed the roofline, a --full figure
+        timing = timing and args.full and not args.no_launch_timing and not use_graph
         cap = (launches // every + 1) * (max(steps, args.warmup + 1))
         warm_timer = _lib.LaunchTimer([timed_kernel], every, cap) if timing else None
         _lib.set_timer(warm_timer)
@@ -662,7 +725,7 @@ def bench_c2(args, ctx):
             if i == 0:
                 marks[0].record()
             st, info = alg.step(keys[(args.warmup + i) % len(keys)], box["state"])
-            box["state"] = st
+            box["state"], box["info"] = st, info
             acc_sum.add_(info.acceptance_rate.mean())
             if collect_draws:
                 draws.append(st.position[:n_sub].clone())
@@ -670,20 +733,24 @@ def bench_c2(args, ctx):
 
         dt, per, t_enq = timed_region(ctx, one, steps)
         _lib.set_timer(None)
+        if dump and args.dump_outputs and rank == 0:
+            write_outputs(args.dump_outputs, {"state": box["state"], "info": box["info"]}, N)
         # host cost of issuing ONE transition into an empty queue (outside the timed region): the
         # in-region enqueue time below also contains the time launch calls block once the host has
         # run ahead as far as the queue allows, so it tracks the GPU time, not the host's work
-        torch.cuda.synchronize()
-        t_i = time.perf_counter()
-        alg.step(prime_key, box["state"])
-        t_issue = time.perf_counter() - t_i
-        torch.cuda.synchronize()
+        t_issue = None
+        if args.full:
+            torch.cuda.synchronize()
+            t_i = time.perf_counter()
+            alg.step(prime_key, box["state"])
+            t_issue = (time.perf_counter() - t_i) * 1e3
+            torch.cuda.synchronize()
         res = {"chain_block": chain_block, "hip_graph": bool(use_graph), "streams": streams, "dt": dt,
                "per_rank_dt": per,
                "steps": steps, "ms_per_step": dt / steps * 1e3,
                "value": world * N * L * steps / dt,
                "host_enqueue_ms_per_step": t_enq / max(steps, 1) * 1e3,
-               "host_issue_ms_unthrottled": t_issue * 1e3,
+               "host_issue_ms_unthrottled": t_issue,
                "gpu_ms_of_each_step": [round(a.elapsed_time(b), 3) for a, b in zip(marks, marks[1:])],
                "mean_acceptance": float(acc_sum.item()) / max(steps, 1), "draws": draws,
                "state": box["state"], "launch": None,
@@ -750,12 +817,12 @@ def bench_c2(args, ctx):
             return 0.5 * (q * g).sum(-1), g
 
         bjx.returns_pair(only_fn)
-    head = measure(best[0], best[1], True, streams=best[2], fn=only_fn,
-                   timing=only_fn is None)  # THE timed region
+    head = measure(best[0], best[1], args.full, streams=best[2], fn=only_fn,
+                   timing=only_fn is None, dump=True)  # THE timed region
     final_draws = ctx.gather_rows(head["state"].position[:256])  # the only thing that crosses xGMI
 
     # ---- extra regions (rank 0 timing only matters; all ranks run them so barriers line up)
-    extras = not args.headline_only and not args.only_mode
+    extras = args.full and not args.headline_only and not args.only_mode
     stream_m = cache_m = None
     # (every rank takes the same branches here: the extra regions contain barriers)
     if head["timed"] and head["streams"] == 1:  # concurrent blocks share the chip: not a clean per-launch time
@@ -1004,7 +1071,7 @@ def bench_c2(args, ctx):
                                    "50 * 2*asin(0.105) = 10.5 rad, not a multiple of 2*pi"})
 
     parity = None
-    if rank == 0 and not args.no_parity and not args.only_mode and not args.headline_only:
+    if rank == 0 and args.full and not args.no_parity and not args.only_mode and not args.headline_only:
         parity = _try_parity(parity_c2, bjx, dev, rank, head["state"], target, imm, inv_var, N, D, L, args.eps,
                              (head["chain_block"], head["hip_graph"], head["streams"]))
     if rank != 0:
@@ -1076,7 +1143,7 @@ def bench_c4(args, ctx):
     launches = L * ((N + blk - 1) // blk)
     every = args.time_every or (16 if launches >= 100 else 1)
     timer = None
-    if rank == 0 and not args.no_launch_timing:
+    if rank == 0 and args.full and not args.no_launch_timing:
         timer = _lib.LaunchTimer([timed_kernel], every, (launches // every + 1) * args.steps)
         torch.cuda.synchronize()
         _lib.set_timer(timer)
@@ -1088,6 +1155,8 @@ def bench_c4(args, ctx):
     dt, per, t_enq = timed_region(ctx, whole_run, 1)
     _lib.set_timer(None)
     (state, params), info = box["res"]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {"state": state, "parameters": params, "info": info}, N)
     acc = info.info.acceptance_rate  # (K, N)
     eps_final = params["step_size"]
     pooled = ctx.gather_rows(torch.stack([eps_final.mean(), eps_final.min(), eps_final.max(),
@@ -1098,7 +1167,7 @@ def bench_c4(args, ctx):
     # dual averaging) runs on 8 chains per block: every launch is a few microseconds of GPU work, so the wall time
     # per step is an UPPER bound of what the host needs to issue a step.
     host_issue_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             import types
 
@@ -1195,6 +1264,8 @@ def bench_c3(args, ctx, T=None, lockstep_steps=8):
 
     dt, per, _ = timed_region(ctx, whole_run, 1)
     st_run, _, rinfo = box["res"]
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {"state": st_run, "info": rinfo}, N)
     from blackjax_amd import _nuts as _bnuts
 
     def spec_stats():
@@ -1222,7 +1293,7 @@ def bench_c3(args, ctx, T=None, lockstep_steps=8):
     # ---- the tail-heavy regime: T = 400 (from the second hundred transitions on a handful of chains sit in the
     # funnel's mouth and build depth-10 trees at every transition: 97 % of the run is a few live chains)
     t400 = None
-    if world == 1 and not args.no_c3_t400 and N == 32768 and D == 256:
+    if args.full and world == 1 and not args.no_c3_t400 and N == 32768 and D == 256:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         _, _, ri4 = alg.run(bjx.random.key(1), state, 400, store_positions=False)
@@ -1249,16 +1320,18 @@ def bench_c3(args, ctx, T=None, lockstep_steps=8):
         acc.add_(info.num_integration_steps.sum())
         step_host_ms.append((time.perf_counter() - t_h) * 1e3)  # step() returns when the transition is done (it polls)
 
-    # two untimed calls right before the region: the runs above went through other drivers of the same object, and the
-    # first `step` after them re-records its tail sequences (measured: 27-67 ms for that one call, 4.4-8.3 ms after)
-    for t in range(2):
-        st_w, _ = alg.step(keys[t], st_box["state"])
-    del st_w
-    dt_l, per_l, _ = timed_region(ctx, one_step, lockstep_steps)
-    tot_l = float(ctx.gather_rows(acc.reshape(1, 1)).sum())
+    dt_l = None
+    if args.full:
+        # two untimed calls right before the region: the runs above went through other drivers of the same object, and
+        # the first `step` after them re-records its tail sequences (measured: 27-67 ms for that one call, 4.4-8.3 ms after)
+        for t in range(2):
+            st_w, _ = alg.step(keys[t], st_box["state"])
+        del st_w
+        dt_l, per_l, _ = timed_region(ctx, one_step, lockstep_steps)
+        tot_l = float(ctx.gather_rows(acc.reshape(1, 1)).sum())
     # the same calls on the lockstep tree driver (step_driver="lockstep": rounds 1-4's `step`), rank 0 of a one-GPU run
     lock_cmp = None
-    if world == 1:
+    if args.full and world == 1:
         try:
             alg_lock = bjx.nuts(bjx.targets.NealFunnel(), eps, torch.ones(D, device=dev), max_num_doublings=max_depth,
                                 chain_offset=rank * N, use_graph="auto", step_driver="lockstep")
@@ -1282,7 +1355,7 @@ def bench_c3(args, ctx, T=None, lockstep_steps=8):
 
     # ---- one full-ensemble tick bracketed with HIP events (plain launches, no graph), rank 0
     tick_us = None
-    if rank == 0 and not args.no_launch_timing:
+    if rank == 0 and args.full and not args.no_launch_timing:
         try:
             alg_t = bjx.nuts(bjx.targets.NealFunnel(), eps, torch.ones(D, device=dev), max_num_doublings=max_depth,
                              chain_offset=rank * N, use_graph=False, run_use_graph=False)
@@ -1298,7 +1371,7 @@ def bench_c3(args, ctx, T=None, lockstep_steps=8):
             tick_us = None
             print(f"bench.py: c3 tick bracket failed: {e!r}", file=sys.stderr)
     parity = None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         parity = _try_parity(parity_c3, bjx, dev, rank, alg, st_box["state"], N, D, eps, max_depth)
     if rank != 0:
         return None
@@ -1359,7 +1432,7 @@ def bench_c3(args, ctx, T=None, lockstep_steps=8):
         "mean_depth": float(pooled[:, 2].mean()), "frac_divergent": float(pooled[:, 3].mean()),
         "speculative_tail": spec_T,
         "free_running_T400": t400,
-        "lockstep_step": {
+        "lockstep_step": None if dt_l is None else {
             "value": tot_l / dt_l, "unit": "chain-leapfrog-steps/s", "steps": lockstep_steps,
             "ms_per_transition": dt_l / lockstep_steps * 1e3, "host_ms_of_each_call": step_host_ms,
             "mean_leapfrogs_per_chain_transition": tot_l / (world * N * lockstep_steps),
@@ -1396,7 +1469,7 @@ def bench_c5(args, ctx, steps=None):
         state, info = alg.step(keys[t], state)
     torch.cuda.synchronize()
     timer = None
-    if rank == 0 and not args.no_launch_timing:
+    if rank == 0 and args.full and not args.no_launch_timing:
         timer = _lib.LaunchTimer(["bjx_leapfrog_dense"], every=4, capacity=L * K + 8)
         _lib.set_timer(timer)
     box = {"state": state}
@@ -1404,13 +1477,15 @@ def bench_c5(args, ctx, steps=None):
 
     def one(i):
         st, info = alg.step(keys[args.warmup + i], box["state"])
-        box["state"] = st
+        box["state"], box["info"] = st, info
         acc.add_(info.acceptance_rate.mean())
 
     dt, per, _ = timed_region(ctx, one, K)
     _lib.set_timer(None)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, {"state": box["state"], "info": box["info"]}, N)
     parity = None
-    if rank == 0 and not args.no_parity and D == 512:
+    if rank == 0 and args.full and not args.no_parity and D == 512:
         parity = _try_parity(parity_c5, bjx, dev, rank, alg, box["state"], N, D, L, 0.5, 0.9)
     if rank != 0:
         return None
@@ -1471,6 +1546,7 @@ def sub_configs(args, ctx):
     def run(name, fn, **over):
         a = copy.copy(args)
         a.chains = a.dim = 0
+        a.dump_outputs = None  # --dump-outputs is the headline's
         for k, v in over.items():
             setattr(a, k, v)
         gc.collect()
@@ -1541,6 +1617,13 @@ def main():
                          "(the full object always goes to stderr and gpurun_out/bench_full_latest.json)")
     ap.add_argument("--selftest-control-flow", action="store_true",
                     help="CPU-only exercise of the multi-rank control flow (no GPU work, no measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="every extra measurement and check besides the headline: launch-timed rooflines, the "
+                         "user-callable and ESS regions, parity against the oracle, the CPU baseline, the jax.random "
+                         "pin, the C3 / C5 / C4 sub-objects of the default run, the extra regions of c3 / c4 / c5")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed call returned in its last step as DIR/<name>.npy "
+                         "(rank 0's chains; large arrays as a fixed sample of chains; at most 64 MB)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -1577,7 +1660,7 @@ def main():
             return
         seen = ctx.ranks_seen()
         out = {"c2": bench_c2, "c3": bench_c3, "c4": bench_c4, "c5": bench_c5}[args.config](args, ctx)
-        if (args.config == "c2" and ctx.world == 1 and not ctx.collective and not args.headline_only
+        if (args.full and args.config == "c2" and ctx.world == 1 and not ctx.collective and not args.headline_only
                 and not args.only_mode and not args.no_sub_configs and args.chains == 0 and args.dim == 0):
             out.update(sub_configs(args, ctx))
         if ctx.rank == 0:
@@ -1595,12 +1678,14 @@ def main():
             if distinct != ctx.world:
                 out["n_gpus_note"] = (f"{ctx.world} ranks shared {distinct} device(s) (BJX_BENCH_BACKEND=gloo "
                                       "control-flow test): NOT a multi-GPU figure")
-            if not args.no_rng_pin:
+            if args.full and not args.no_rng_pin:
                 out["rng_pin"] = rng_pin_check(ctx.dev)
-            out["oracle_pin"] = ("the oracle the parity blocks check against is itself pinned on the reference's own source executed on a "
-                                 "stand-in for JAX (tests/refshim; tests/golden/ref_shim_fixtures.json, tests/test_ref_shim_fixtures.py): "
-                                 "every discrete outcome equal, positions to ~1e-6; the jax.random bit streams are NOT pinned by that (rng_pin)")
-            if ctx.world == 1 and not args.no_cpu_baseline and args.config == "c2":
+            if args.full:
+                out["oracle_pin"] = ("the oracle the parity blocks check against is itself pinned on the reference's own source executed "
+                                     "on a stand-in for JAX (tests/refshim; tests/golden/ref_shim_fixtures.json, "
+                                     "tests/test_ref_shim_fixtures.py): every discrete outcome equal, positions to ~1e-6; the "
+                                     "jax.random bit streams are NOT pinned by that (rng_pin)")
+            if args.full and ctx.world == 1 and not args.no_cpu_baseline and args.config == "c2":
                 try:
                     out["cpu_baseline"] = cpu_baseline(args.dim or 1024, args.leapfrogs, args.eps)
                 except Exception as e:  # the baseline is a reported extra; never fail the GPU number

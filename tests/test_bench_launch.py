@@ -51,6 +51,21 @@ def _full(r):
     return j
 
 
+def _load_bench():
+    """bench.py as a module (its main() does not run on import)."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("_bjx_bench", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    argv = sys.argv
+    sys.argv = [BENCH]
+    try:
+        spec.loader.exec_module(bench)
+    finally:
+        sys.argv = argv
+    return bench
+
+
 def test_gpus_flag_refuses_instead_of_running_fewer_ranks():
     n = (torch.cuda.device_count() if torch.cuda.is_available() else 0) + 1
     r = _run(["--gpus", str(max(n, 2))])
@@ -81,7 +96,7 @@ TINY = ["--chains", "4096", "--dim", "256", "--leapfrogs", "6", "--steps", "4", 
 
 @pytest.mark.gpu
 def test_bench_c2_tiny_single_rank_json_contract():
-    r = _run(TINY)
+    r = _run(["--full"] + TINY)
     assert r.returncode == 0, r.stderr[-2000:]
     c = _json_line(r.stdout)  # the compact line of the contract
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
@@ -114,10 +129,61 @@ def test_bench_c2_tiny_single_rank_json_contract():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_what_full_computes(tmp_path):
+    """A run without --full times the headline and nothing else; --dump-outputs writes the last timed step's state and
+    info, and a --full run of the same arguments writes the same arrays (the extra regions come after it)."""
+    r = _run(TINY + ["--dump-outputs", str(tmp_path / "plain")])
+    assert r.returncode == 0, r.stderr[-2000:]
+    c = _json_line(r.stdout)
+    assert c["steps"] == 4 and c["ms_per_step"] > 0 and c["value"] > 0 and c["dtype"] == "f32"
+    for k in ("roofline", "cpu_baseline", "parity", "ess_nonresonant", "torch_callable_mode", "c3_nuts", "rng_pin"):
+        assert k not in c, k
+    j = _full(r)
+    assert j["torch_callable_mode"] is None and j["parity"] is None and j["roofline"] is None
+    r2 = _run(["--full", "--no-cpu-baseline", "--no-torch-callable"] + TINY + ["--dump-outputs", str(tmp_path / "full")])
+    assert r2.returncode == 0, r2.stderr[-2000:]
+    assert _json_line(r2.stdout)["parity"]["accept_mismatches"] == 0
+    _full(r2)
+    names = sorted(p.name for p in (tmp_path / "plain").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "full").iterdir())
+    assert "state.position.npy" in names and "info.acceptance_rate.npy" in names
+    import numpy as np
+
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+    assert np.load(tmp_path / "plain" / "state.position.npy").shape == (4096, 256)
+
+
+def test_write_outputs_samples_chains_within_the_size_bound(tmp_path):
+    """--dump-outputs on the default C2 shape (65 536 chains x 1 024): float32 / float64 files, large arrays cut to a
+    fixed sample of chains named in chain_sample.npy, per-chain vectors whole, at most 64 MB in all."""
+    import numpy as np
+
+    bench = _load_bench()
+    N, D = 65536, 1024
+    g = torch.Generator().manual_seed(0)
+    tree = {"state": {"position": torch.randn(N, D, generator=g), "logdensity": torch.randn(N, generator=g)},
+            "info": {"is_accepted": torch.rand(N, generator=g) < 0.5, "steps": 50, "none": None}}
+    bench.write_outputs(str(tmp_path), tree, N)
+    files = {p.name: np.load(p) for p in tmp_path.iterdir()}
+    assert sorted(files) == ["chain_sample.npy", "info.is_accepted.npy", "info.steps.npy", "state.logdensity.npy",
+                             "state.position.npy"]
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 * 10 ** 6
+    idx = files["chain_sample.npy"].astype(np.int64)
+    assert files["state.position.npy"].dtype == np.float32 and files["state.position.npy"].shape == (len(idx), D)
+    np.testing.assert_array_equal(files["state.position.npy"], tree["state"]["position"].numpy()[idx])
+    np.testing.assert_array_equal(files["state.logdensity.npy"], tree["state"]["logdensity"].numpy())
+    assert files["info.is_accepted.npy"].dtype == np.float64 and files["info.steps.npy"] == 50.0
+    bench.write_outputs(str(tmp_path / "again"), tree, N)  # the sample depends on the chain count alone
+    np.testing.assert_array_equal(np.load(tmp_path / "again" / "chain_sample.npy"), files["chain_sample.npy"])
+
+
+@pytest.mark.gpu
 def test_bench_two_gloo_ranks_share_one_gpu():
     """The real bench under its own launcher with 2 ranks (gloo, both on cuda:0 of a 1-GPU box):
     n_gpus = 2, twice the chains, both ranks seen."""
-    r = _run(["--gpus", "2", "--no-cpu-baseline"] + TINY, {"BJX_BENCH_BACKEND": "gloo"})
+    r = _run(["--gpus", "2", "--full", "--no-cpu-baseline"] + TINY, {"BJX_BENCH_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     c = _json_line(r.stdout)
     assert c["n_gpus"] == 1 and c["ranks"] == 2 and "cpu_baseline" not in c
@@ -132,7 +198,7 @@ def test_bench_two_gloo_ranks_share_one_gpu():
 
 @pytest.mark.gpu
 def test_bench_c4_tiny():
-    r = _run(["--config", "c4", "--chains", "1024", "--dim", "512", "--leapfrogs", "5", "--steps", "24",
+    r = _run(["--full", "--config", "c4", "--chains", "1024", "--dim", "512", "--leapfrogs", "5", "--steps", "24",
               "--warmup", "2"])
     assert r.returncode == 0, r.stderr[-2000:]
     assert _json_line(r.stdout)["roofline"]["bound"] == "hbm"
@@ -143,7 +209,7 @@ def test_bench_c4_tiny():
 
 @pytest.mark.gpu
 def test_bench_c3_tiny():
-    r = _run(["--config", "c3", "--chains", "512", "--dim", "64", "--steps", "6", "--warmup", "2"])
+    r = _run(["--full", "--config", "c3", "--chains", "512", "--dim", "64", "--steps", "6", "--warmup", "2"])
     assert r.returncode == 0, r.stderr[-2000:]
     assert _json_line(r.stdout)["config"]["workload"].startswith("C3: NUTS")
     j = _full(r)
@@ -155,7 +221,7 @@ def test_bench_c3_tiny():
 
 @pytest.mark.gpu
 def test_bench_c5_tiny():
-    r = _run(["--config", "c5", "--chains", "1024", "--dim", "128", "--steps", "3", "--warmup", "1"])
+    r = _run(["--full", "--config", "c5", "--chains", "1024", "--dim", "128", "--steps", "3", "--warmup", "1"])
     assert r.returncode == 0, r.stderr[-2000:]
     assert _json_line(r.stdout)["roofline"]["bound"] == "mfma"
     j = _full(r)
@@ -167,9 +233,9 @@ def test_bench_c5_tiny():
 
 @pytest.mark.gpu
 def test_bench_default_line_carries_c3_c5_c4_sub_objects():
-    """The default run (no --chains / --dim): C2 headline + BASELINE.json configs[2..4] as sub-objects.
+    """The default --full run (no --chains / --dim): C2 headline + BASELINE.json configs[2..4] as sub-objects.
     Shortened with --steps; the sub-objects keep their own step counts."""
-    r = _run(["--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-torch-callable", "--no-ess-nonresonant"],
+    r = _run(["--full", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--no-torch-callable", "--no-ess-nonresonant"],
              timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     c = _json_line(r.stdout)  # the compact line carries every config's value, roofline fraction and parity counts
@@ -192,16 +258,7 @@ def test_compact_line_of_a_committed_full_record_fits_the_drivers_tail():
     """the driver keeps an 8 KB tail of stdout.  `bench.compact_line` on the committed full record of
     round 6 (profiles/r06/bench_final_r06.json, ~26 KB): at most 6 000 bytes, one JSON object, and it carries the
     contract keys, the roofline / cpu_baseline objects, every config's value, roofline fraction and parity counts."""
-    import importlib.util
-
-    spec = importlib.util.spec_from_file_location("_bjx_bench", BENCH)
-    bench = importlib.util.module_from_spec(spec)
-    argv = sys.argv
-    sys.argv = [BENCH]
-    try:
-        spec.loader.exec_module(bench)
-    finally:
-        sys.argv = argv
+    bench = _load_bench()
     full = json.load(open(os.path.join(ROOT, "profiles", "r06", "bench_final_r06.json")))
     assert len(json.dumps(full)) > 15000
     line = bench.compact_line(full, "gpurun_out/bench_full_latest.json")

@@ -84,7 +84,12 @@ def test_product_factor_equals_oracle_factor(D, rho):
     got, ref = pm.mass_sqrt_t.numpy().T, mo.mass_matrix_sqrt
     assert got.dtype == f32 and ref.dtype == f32
     np.testing.assert_allclose(got, ref, rtol=2.5e-7, atol=1e-9)
-    assert np.mean(got == ref) > 0.9  # (measured: 94-100 % of the entries are the same float, the rest one ulp apart)
+    # The factor of an AR(1) matrix is bidiagonal: every entry off the band is cancellation residue (|x| <= 1.1e-6 at
+    # D = 512, against a diagonal of ~2.3) whose low bits depend on the blocking of the LAPACK build and the CPU code
+    # path it dispatches to (MKL in torch, OpenBLAS in NumPy: 83-94 % of ALL entries equal across hosts), bounded by
+    # the assert_allclose above.  The band itself is the same float on every code path measured.
+    band = np.abs(idx[:, None] - idx[None, :]) <= 1
+    np.testing.assert_array_equal(got[band], ref[band])
     # upper-triangular (S = L^{-T}); S S^T = imm^{-1}, i.e. with L = S^{-T}: L L^T = imm
     assert np.all(np.tril(got, -1) == 0)
     L = np.linalg.inv(got.astype(f64)).T

@@ -10,7 +10,7 @@ rm -rf $O; mkdir -p $O
 cd $R
 (time timeout 1200 python -m pytest tests/ -q -m gpu -p no:cacheprovider) > $O/gpu_tests.log 2>&1
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python tools/bench_nuts_spec.py --T 20 100 400 --reps 1 --spec 0 128 > $O/nuts_c3_spec_ab.json 2> $O/spec_ab.err
 python tools/step_vs_run1.py > $O/nuts_c3_step_drivers.json 2> $O/step.err
 cd /tmp; export TMPDIR=/tmp

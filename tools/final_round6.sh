@@ -9,7 +9,7 @@ rm -rf $O; mkdir -p $O
 cd $R
 (time timeout 1500 python -m pytest tests/ -q -m gpu) > $O/gpu_tests.log 2>&1
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-BJX_BENCH_FULL=$O/bench_full.json python bench.py > $O/bench_compact.json 2> $O/bench.err
+BJX_BENCH_FULL=$O/bench_full.json python bench.py --full > $O/bench_compact.json 2> $O/bench.err
 python tools/time_momentum.py > $O/momentum.json 2>> $O/bench.err
 bash tools/rocprof_kernel.sh final6/kt_dense k_dense_gemm_tn8 python bench.py --config c5 --no-cpu-baseline --no-parity --steps 20 > $O/dense_kernel_stats.txt 2>&1
 bash tools/rocprof_kernel.sh final6/kt_nuts "k_nuts_async_tick3|k_neal_funnel|k_nuts_spec" python bench.py --config c3 --no-cpu-baseline --no-parity --no-c3-t400 > $O/nuts_kernel_stats.txt 2>&1
