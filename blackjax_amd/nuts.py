@@ -25,11 +25,15 @@ callable that cannot be recorded.
 from __future__ import annotations
 
 import ctypes
+import os
+import time
 from typing import Callable, NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _lib, integrators, metrics
+from . import random as bjx_random
 from ._util import (new_graph, record_graph, check_batch, eval_logdensity, is_capturable, step_size_args, value_and_grad,
                     warn_eager_driver)
 from .base import SamplingAlgorithm
@@ -55,21 +59,36 @@ class NUTSInfo(NamedTuple):
     acceptance_rate: torch.Tensor
 
 
-def _make_info(p0, bufs, fs, is_, clone: bool):
+def _tree_buffers(N, D, max_depth, device, zero_ints=False):
+    """The tree state of N transitions (``bjx_nuts_t``): the ``_BUFS`` arrays, the U-turn checkpoint stacks
+    ``ckpt_r`` / ``ckpt_rs`` and the scalar tables ``fs`` / ``is_``.  -> (those tensors, their ``NutsDesc`` pointer
+    fields), both keyed by the descriptor's field names.  ``zero_ints``: ``is_`` starts zeroed, as the free-running
+    driver has it; the lockstep drivers skip that fill (one more launch per step)."""
+    f32 = dict(dtype=torch.float32, device=device)
+    tree = {n: torch.empty((N, D), **f32) for n in _BUFS}
+    tree["ckpt_r"] = torch.empty((N, max(max_depth, 1), D), **f32)
+    tree["ckpt_rs"] = torch.empty_like(tree["ckpt_r"])
+    tree["fs"] = torch.empty((_lib.NUTS_NF, N), **f32)
+    tree["is_"] = (torch.zeros if zero_ints else torch.empty)((_lib.NUTS_NI, N), dtype=torch.int32, device=device)
+    return tree, {n: t.data_ptr() for n, t in tree.items()}
+
+
+def _make_info(p0, tree, clone: bool):
     F, I = _lib.NUTS_F, _lib.NUTS_I
+    fs, is_ = tree["fs"], tree["is_"]
     c = (lambda t: t.clone()) if clone else (lambda t: t)
     info = NUTSInfo(
         p0,
         is_[I["DIV"]].bool(),
         is_[I["TURN"]].bool(),
         c(fs[F["PENERGY"]]),
-        IntegratorState(c(bufs["Lq"]), c(bufs["Lp"]), c(fs[F["LLOGP"]]), c(bufs["Lg"])),
-        IntegratorState(c(bufs["Rq"]), c(bufs["Rp"]), c(fs[F["RLOGP"]]), c(bufs["Rg"])),
+        IntegratorState(c(tree["Lq"]), c(tree["Lp"]), c(fs[F["LLOGP"]]), c(tree["Lg"])),
+        IntegratorState(c(tree["Rq"]), c(tree["Rp"]), c(fs[F["RLOGP"]]), c(tree["Rg"])),
         c(is_[I["DEPTH"]]),
         c(is_[I["NSTATES"]]),
         c(fs[F["ACC"]]),
     )
-    return HMCState(c(bufs["Pq"]), c(fs[F["PLOGP"]]), c(bufs["Pg"])), info
+    return HMCState(c(tree["Pq"]), c(fs[F["PLOGP"]]), c(tree["Pg"])), info
 
 
 def _dense_fields(kind, imm, N, D, max_depth, device):
@@ -89,7 +108,7 @@ class _GraphWorkspace:
     """Static device buffers + captured chunk graphs for the ``use_graph`` driver."""
 
     MAX_CHUNK = 16
-    MIN_BUCKET = int(__import__("os").environ.get("BJX_NUTS_MIN_BUCKET", "256"))  # smallest recorded batch
+    MIN_BUCKET = int(os.environ.get("BJX_NUTS_MIN_BUCKET", "256"))  # smallest recorded batch
 
     def __init__(self, N, D, max_depth, vg, imm_shape, kind, thr, device, owner=None,
                  kick_c=(0.5, 0.5), drift_c=(1.0,)):
@@ -97,11 +116,7 @@ class _GraphWorkspace:
         self.kick_c, self.drift_c = tuple(kick_c), tuple(drift_c)  # palindromic integrator [b1, a1, ..., b1]
         self.owner = owner  # the user's callable: held so that id(owner) in the workspace key stays unique
         f32 = dict(dtype=torch.float32, device=device)
-        self.bufs = {n: torch.empty((N, D), **f32) for n in _BUFS}
-        self.ck_r = torch.empty((N, max(max_depth, 1), D), **f32)
-        self.ck_rs = torch.empty_like(self.ck_r)
-        self.fs = torch.empty((_lib.NUTS_NF, N), **f32)
-        self.is_ = torch.empty((_lib.NUTS_NI, N), dtype=torch.int32, device=device)
+        self.tree, tree_f = _tree_buffers(N, D, max_depth, device)
         self.eps = torch.ones(N, **f32)
         self.imm = torch.ones(imm_shape, **f32)  # static copy of the (diag or dense) metric
         self.idx = torch.arange(N, dtype=torch.int32, device=device)
@@ -118,9 +133,7 @@ class _GraphWorkspace:
             imm_stride=D if (kind == "diag" and len(imm_shape) == 2) else 0,
             eps_per_chain=self.eps.data_ptr(), eps=0.0,
             divergence_threshold=thr, key0=0, key1=0, chain_offset=0, step_fold=-1,
-            q0=0, g0=0, p0=0, ckpt_r=self.ck_r.data_ptr(), ckpt_rs=self.ck_rs.data_ptr(),
-            fs=self.fs.data_ptr(), is_=self.is_.data_ptr(),
-            **{n: b.data_ptr() for n, b in self.bufs.items()}, **self.dense["fields"],
+            q0=0, g0=0, p0=0, **tree_f, **self.dense["fields"],
             int_kick=self.kick_c[0], int_drift=self.drift_c[0])
         self.graphs: dict = {}
         self.count_pinned = torch.zeros(1, dtype=torch.int64).pin_memory()  # lagged reads of ctl[2] (kernel_graph)
@@ -260,11 +273,8 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: i
          v0) = _common(rng_key, state, logdensity_fn, step_size, inverse_mass_matrix, chain_offset)
         dev = q0.device
         max_depth = int(max_num_doublings)
-        bufs = {n: torch.empty_like(q0) for n in _BUFS}
-        ck_r = torch.empty((N, max(max_depth, 1), D), dtype=torch.float32, device=dev)
-        ck_rs = torch.empty_like(ck_r)
-        fs = torch.empty((_lib.NUTS_NF, N), dtype=torch.float32, device=dev)
-        is_ = torch.empty((_lib.NUTS_NI, N), dtype=torch.int32, device=dev)
+        tree, tree_f = _tree_buffers(N, D, max_depth, dev)
+        is_ = tree["is_"]
         gemm = metric.kind == "dense_gemm"
         dense_f = _dense_fields("dense" if gemm else metric.kind, metric.imm, N, D, max_depth, dev)
         if v0 is not None:
@@ -277,9 +287,7 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: i
             N=N, D=D, max_depth=max_depth, reserved=0, imm=metric.imm.data_ptr(),
             imm_stride=metric.imm_stride, eps_per_chain=_lib.ptr(eps_pc), eps=eps,
             divergence_threshold=thr, key0=k0, key1=k1, chain_offset=int(chain_offset),
-            step_fold=fold, q0=q0.data_ptr(), g0=g0.data_ptr(), p0=p0.data_ptr(),
-            ckpt_r=ck_r.data_ptr(), ckpt_rs=ck_rs.data_ptr(), fs=fs.data_ptr(), is_=is_.data_ptr(),
-            **{n: b.data_ptr() for n, b in bufs.items()}, **dense_f["fields"],
+            step_fold=fold, q0=q0.data_ptr(), g0=g0.data_ptr(), p0=p0.data_ptr(), **tree_f, **dense_f["fields"],
             int_kick=kick_c[0], int_drift=drift_c[0])
         dref = ctypes.byref(desc)
         _lib.call("bjx_nuts_init", stream, dref, logp0.data_ptr(), ke0.data_ptr())
@@ -339,7 +347,7 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: i
                           qf.data_ptr(), logp_f.data_ptr(), gf.data_ptr(), 1 if fuse else 0)
                 need_pre = not fuse
             _lib.call("bjx_nuts_merge", stream, dref, depth, n_doubling, _lib.ptr(idx_doubling))
-        return _make_info(p0, bufs, fs, is_, clone=False)
+        return _make_info(p0, tree, clone=False)
 
     def kernel_graph(rng_key, state: HMCState, logdensity_fn: Callable, step_size,
                      inverse_mass_matrix, max_num_doublings: int = 10, *, chain_offset: int = 0):
@@ -428,7 +436,7 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: i
                     n_cap = ws.bucket(n_now)
             del stopped
             _lib.call("bjx_nuts_merge", stream, dref, depth, n_doubling, idx_doubling.data_ptr())
-        return _make_info(p0, ws.bufs, ws.fs, ws.is_, clone=True)
+        return _make_info(p0, ws.tree, clone=True)
 
     not_capturable: dict = {}  # id -> callable whose capture failed once (the reference pins the id)
 
@@ -453,12 +461,6 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: i
     if use_graph == "auto":
         return kernel_auto
     return kernel_graph if use_graph else kernel_eager
-
-
-def _os_environ():
-    import os
-
-    return os.environ
 
 
 def free_running_supports(integrator, metric_kind: str, dim: int) -> bool:
@@ -525,17 +527,6 @@ def _warn_lockstep_run(integrator, metric_kind: str, dim: int) -> None:
         "transition waits for the deepest tree of the ensemble.", RuntimeWarning, stacklevel=3)
 
 
-def auto_row_block(n_rows: int, dim: int) -> int:
-    """Rows per group of the free-running schedule.  Default: ALL rows in one group.  Ticking the
-    ensemble in Infinity-Cache-sized row groups (the analogue of ``hmc.auto_chain_block``; pass
-    ``row_block=n`` to ``run_free``) was measured SLOWER at the C3 shape (32 768 x
-    256: one group 138.6 M/s, groups of 16 384 / 8 192 / 4 096 rows 124.6 / 114.2 / 88.9 M/s; on the
-    final kernels 184-191 vs 164 / 131): a tick moves more than the cache holds between two uses of
-    a row whatever the grouping, and the smaller launches cost (NOTEBOOK.md section 7).  Round 6: two half-size
-    groups on two CONCURRENT streams (one group's tick under the other's callable): 276 vs 279 M/s at T = 100, no gain."""
-    return int(n_rows)
-
-
 class NUTSRunInfo(NamedTuple):
     """Per-(transition, chain) records of a free-running run, each ``(num_steps, N)``: the scalar
     fields of ``NUTSInfo`` plus the log-density of the accepted state."""
@@ -550,13 +541,784 @@ class NUTSRunInfo(NamedTuple):
     step_size: Optional[torch.Tensor] = None  # adaptation runs only: the step size after transition t's update
 
 
+def _run_info(T, N, device, step_size=None):
+    """A ``NUTSRunInfo`` of uninitialised ``(T, N)`` arrays."""
+    dtypes = (torch.float32,) * 3 + (torch.int32,) * 2 + (torch.bool,) * 2
+    return NUTSRunInfo(*(torch.empty((T, N), dtype=dt, device=device) for dt in dtypes), step_size)
+
+
+class _LaggedCount:
+    """Lagged reads of the finished-chain count ``n_done``: the count is copied to pinned host memory behind every batch
+    of launches and the host reads the copy of the PREVIOUS batch, so the next batch is always queued before the host
+    waits -- the GPU never idles on the round trip of a blocking .item() (0.5-1 us per tick of a 12 us tick).  The count
+    only grows: a stale (smaller) value is safe for the tier choice, and the run ends at most one batch late (ticks over
+    finished chains do nothing)."""
+
+    def __init__(self, n_done):
+        self.n_done = n_done
+        self.pinned = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(2)]
+        self.events = [torch.cuda.Event() for _ in range(2)]
+        self.slot, self.primed, self.last = 0, False, 0
+
+    def reset(self, last):
+        """The next read only queues a copy and returns ``last``, the count known so far."""
+        self.primed, self.last = False, last
+
+    def read(self):
+        k = self.slot
+        self.pinned[k].copy_(self.n_done, non_blocking=True)
+        self.events[k].record()
+        self.slot = k ^ 1
+        if self.primed:
+            self.events[k ^ 1].synchronize()
+            self.last = int(self.pinned[k ^ 1][0])
+        self.primed = True
+        return self.last
+
+
+class _Batch:
+    """The busy phase's batch: compact rows ticked together -- their pending positions
+    ``qf``, the callable's ``(logp_f, gf)`` on them -- and their row list (``None``: row b is chain b)."""
+
+    def __init__(self, fr, rows, n_rows, qf):
+        self.rows, self.n_rows, self.qf = rows, n_rows, qf
+        self.run = fr.make_run(rows, n_rows)
+        self.rref = ctypes.byref(self.run)
+        self.logp_f = torch.zeros(n_rows, dtype=torch.float32, device=qf.device)  # the first tick only starts transitions
+        self.gf = torch.zeros_like(qf)
+        self.graph = None  # (CUDAGraph, static logp_f, static gf, n_ticks)
+        self.eager_chunks = 0
+
+    def chunk(self, fr, n_ticks, logp_f, gf):
+        """``n_ticks`` ticks, each followed by the callable on the batch."""
+        run = self.run
+        if fr.fused:
+            # engine-resident target + one-launch ticks: the whole chunk is ONE launch, every wave
+            # advancing its chain n_ticks times (bjx_nuts_async_t.ticks_per_launch)
+            run.tick, run.ticks_per_launch = 0, n_ticks
+            fr.multi_tick(run, self.qf, logp_f, gf)
+            return logp_f, gf
+        dref, rref, qf, vg = fr.dref, self.rref, self.qf, fr.vg
+        for i in range(n_ticks):
+            run.tick = i & 1
+            _lib.call("bjx_nuts_async_tick", _lib.current_stream(), dref, rref, qf.data_ptr(), logp_f.data_ptr(),
+                      gf.data_ptr())
+            logp_f, gf = eval_logdensity(vg, qf)
+        return logp_f, gf
+
+    def _chunk_into(self, fr, n_ticks, lp_s, g_s):
+        """``chunk`` ending in the static ``(lp_s, g_s)`` of a recording."""
+        lp_e, g_e = self.chunk(fr, n_ticks, lp_s, g_s)
+        if lp_e is not lp_s:
+            lp_s.copy_(lp_e)
+            g_s.copy_(g_e)
+
+    def advance(self, fr, n_ticks, record):
+        if self.graph is not None and self.graph[3] == n_ticks:
+            self.graph[0].replay()
+            return
+        self.graph = None
+        self.logp_f, self.gf = self.chunk(fr, n_ticks, self.logp_f, self.gf)
+        self.eager_chunks += 1
+        if record:
+            # recording does not execute anything, so the chains' state is untouched by it
+            lp_s, g_s = self.logp_f.clone(), self.gf.clone()
+            cg = fr.record(self._chunk_into, fr, n_ticks, lp_s, g_s)
+            if cg is not None:
+                self.graph = (cg, lp_s, g_s, n_ticks)
+                self.logp_f, self.gf = lp_s, g_s
+
+
+class _Tail:
+    """The tail of a run (at most ``cap`` live rows) on FIXED-CAPACITY buffers: the kernels read
+    the live-row count from device memory (``n_rows_dev``, include/bjx_nuts.h), so ONE recorded
+    chunk of ticks per (buffer set, view size) serves every batch size in between -- compaction
+    only rewrites the row list, the pending positions and the count.  Two buffer sets because a
+    compaction cannot work in place.
+
+    Round 3: the launch geometry and the callable's batch follow TIERS of the live-row count
+    (``cap``, then 4 096, 2 048, 512, 128, 32 rows: prefix views of the same buffers, one recording each) instead
+    of staying at ``cap`` to the end: with three live chains the callable used to be evaluated on
+    all ``cap`` rows every tick.  Round 6: ``cap`` is up to 8 192 rows (2 048 before) -- between 2 048 and 8 192 live
+    rows a tick is 16-20 us of GPU work and plain launches from Python took 33 us (NOTEBOOK section 19).  Rows of a view beyond the live count always hold a
+    VALID position (the buffers start as copies of a current chain state and are only ever
+    overwritten with pending positions), so a log-density that validates its support never sees
+    zeros or garbage there."""
+
+    TIERS = (32, 128, 512, 2048, 4096)
+    # a recorded sequence of n_ticks ticks, replayed REPS times per host sync: recording costs ~40 us per tick,
+    # so a short sequence pays for itself within a few hundred ticks
+    REPS = 4
+
+    def __init__(self, fr, cap):
+        self.cap, self.n_ticks = cap, fr.sync_every
+        i32 = dict(dtype=torch.int32, device=fr.dev)
+        self.rows = [torch.zeros(cap, **i32) for _ in range(2)]
+        # valid positions everywhere.  repeat(), not expand().contiguous(): with cap == 1 the latter IS q[:1] (already
+        # contiguous, no copy), and the last live chain's pending positions were then written into chain 0's state
+        # row (round 5: found by the row-width sweep of tests/test_nuts_v3_gpu.py; latent since round 3)
+        self.qf = [fr.q[:1].repeat(cap, 1) for _ in range(2)]
+        self.n_dev = [torch.zeros(1, **i32) for _ in range(2)]
+        self.run = []
+        for k in range(2):
+            r = fr.make_run(self.rows[k], cap)
+            r.n_rows_dev = self.n_dev[k].data_ptr()
+            self.run.append(r)
+        self.graph = {}   # (buffer set, view rows) -> (CUDAGraph, ticks per replay)
+        self.cur, self.n_cur, self.view = 0, 0, cap
+        if fr.fused:  # in/out (logp, grad) of the pending positions, one pair per buffer set
+            self.lp = [torch.zeros(cap, dtype=torch.float32, device=fr.dev) for _ in range(2)]
+            self.g = [torch.zeros((cap, fr.D), dtype=torch.float32, device=fr.dev) for _ in range(2)]
+
+    def tier(self, n_active):
+        for v in self.TIERS:
+            if n_active <= v and v < self.cap:
+                return v
+        return self.cap
+
+    def _after_compaction(self, fr, k, n_active):
+        self.view = self.tier(n_active)
+        self.run[k].n_rows = self.view
+        self.cur, self.n_cur = k, n_active
+        if fr.fused:  # (logp, grad) of the gathered positions: one stand-alone evaluation, then in place
+            lp, g_ = eval_logdensity(fr.vg, self.qf[k][:self.view])
+            self.lp[k][:self.view].copy_(lp)
+            self.g[k][:self.view].copy_(g_)
+
+    def enter(self, fr, batch, n_active):
+        fr.compact(batch.rref, batch.qf, self.rows[0], self.qf[0], fr.n_out)
+        self.n_dev[0].fill_(n_active)
+        self._after_compaction(fr, 0, n_active)
+
+    def compact(self, fr, n_active):
+        x, y = self.cur, self.cur ^ 1
+        fr.compact(ctypes.byref(self.run[x]), self.qf[x], self.rows[y], self.qf[y], self.n_dev[y])
+        self._after_compaction(fr, y, n_active)
+
+    def _body(self, fr, k, n_ticks):
+        """``n_ticks`` x (callable on the pending positions, tick).  CALLABLE FIRST: what carries
+        over from one sequence to the next is then ``qf`` alone -- a fixed buffer the last tick
+        wrote -- and a replay needs no copies of the callable's outputs into static inputs (round 2
+        copied logp and the gradient once per sequence: 0.85 us per tick in the deep tail)."""
+        run_k = self.run[k]
+        qf_v = self.qf[k][:self.view]
+        if fr.fused:
+            run_k.tick, run_k.ticks_per_launch = 0, n_ticks  # the whole sequence as one launch
+            fr.multi_tick(run_k, qf_v, self.lp[k][:self.view], self.g[k][:self.view])
+            return
+        dref, rref_k, vg = fr.dref, ctypes.byref(run_k), fr.vg
+        for i in range(n_ticks):
+            lp, g_ = eval_logdensity(vg, qf_v)
+            run_k.tick = i & 1
+            _lib.call("bjx_nuts_async_tick", _lib.current_stream(), dref, rref_k, qf_v.data_ptr(),
+                      lp.data_ptr(), g_.data_ptr())
+
+    def advance(self, fr):
+        """-> ticks issued"""
+        k = self.cur
+        hit = self.graph.get((k, self.view))
+        if hit is not None:
+            for _ in range(self.REPS):
+                hit[0].replay()
+            return hit[1] * self.REPS
+        # ticks per recorded sequence: the few-row tiers are pure launch latency (two dependent kernels per tick), so
+        # their sequences are longer -- fewer replay boundaries per tick
+        n = self.n_ticks * (4 if self.view <= 128 else 1)
+        self._body(fr, k, self.n_ticks)  # one short plain sequence first (kernels, allocator warm)
+        if fr.can_record:
+            cg = fr.record(self._body, fr, k, n)
+            if cg is not None:
+                self.graph[(k, self.view)] = (cg, n)
+        return self.n_ticks
+
+
+class _SpecTail:
+    """The two-stream speculative tail (include/bjx_nuts.h): stream A = the current stream, [callable, integrate]
+    per leapfrog as one recorded sequence; stream B = ``side``, one long-lived bookkeeping launch per sequence."""
+
+    RING = 64      # ring slots per row
+    LEAD = 4       # records the integrator may run ahead of the bookkeeper's consumed count (2: stalls; 4 .. 63: flat at
+                   # D = 256, where a record costs the bookkeeper 3.2 us against 4.9 us per leaf on stream A)
+    SEQ0 = 8       # plain leapfrogs before the recording (kernels, allocator warm)
+    TIMEOUT_US = 20000
+
+    def __init__(self, fr, cap):
+        self.cap = cap
+        self.seq, self.reps = fr.spec_seq, fr.spec_reps
+        D, i32 = fr.D, dict(dtype=torch.int32, device=fr.dev)
+        self.rows = torch.zeros(cap, **i32)
+        self.qf = fr.q[:1].repeat(cap, 1)  # valid positions everywhere (see _Tail)
+        self.n_dev = torch.zeros(1, **i32)
+        mk = lambda: torch.zeros((cap, D), dtype=torch.float32, device=fr.dev)  # noqa: E731
+        self.fp, self.qf_book = mk(), mk()
+        self.ends = [mk() for _ in range(6)]
+        self.iw = torch.zeros((cap, _lib.NUTS_SPEC_IW), **i32)
+        self.bw = torch.zeros((cap, _lib.NUTS_SPEC_IW), **i32)
+        self.ring_g = torch.zeros((cap, self.RING, D), dtype=torch.float32, device=fr.dev)
+        self.ring_tag = torch.zeros((cap, self.RING, _lib.NUTS_SPEC_TAG), **i32)
+        self.avail = torch.zeros(cap, **i32)
+        self.ack = torch.zeros(cap, dtype=torch.int64, device=fr.dev)
+        self.a_seq = torch.zeros(1, **i32)
+        self.dbg = torch.zeros(8, **i32)
+        self.run = fr.make_run(self.rows, cap)
+        self.run.n_rows_dev = self.n_dev.data_ptr()
+        e = self.ends
+        self.spec = _lib.NutsSpec(
+            n_rows=cap, n_rows_dev=self.n_dev.data_ptr(), rows=self.rows.data_ptr(), ring=self.RING,
+            lead=self.LEAD,
+            qf=self.qf.data_ptr(), fp=self.fp.data_ptr(), eLq=e[0].data_ptr(), eLp=e[1].data_ptr(),
+            eLg=e[2].data_ptr(), eRq=e[3].data_ptr(), eRp=e[4].data_ptr(), eRg=e[5].data_ptr(),
+            iw=self.iw.data_ptr(), ring_g=self.ring_g.data_ptr(), ring_tag=self.ring_tag.data_ptr(),
+            avail=self.avail.data_ptr(), ack=self.ack.data_ptr(), qf_book=self.qf_book.data_ptr(), bw=self.bw.data_ptr(),
+            a_seq=self.a_seq.data_ptr(), dbg=self.dbg.data_ptr())
+        self.rref, self.sref = ctypes.byref(self.run), ctypes.byref(self.spec)
+        self.side = fr.side_stream
+        self.graph = None
+        self.seq_no = 0
+        self.t_enter = time.perf_counter()
+
+    def enter(self, fr, src_rref, src_qf):
+        """Live rows of the source batch (between two ticks) -> this tail."""
+        fr.compact(src_rref, src_qf, self.rows, self.qf, self.n_dev)
+        _lib.call("bjx_nuts_spec_enter", fr.stream, fr.dref, self.rref, self.sref)
+        self.side.wait_stream(torch.cuda.current_stream(fr.dev))
+
+    def _seq_a(self, fr, n):
+        dref, rref, sref, vg, qf = fr.dref, self.rref, self.sref, fr.vg, self.qf
+        for i in range(n):
+            lp, g_ = eval_logdensity(vg, qf)
+            _lib.call("bjx_nuts_spec_integrate", _lib.current_stream(), dref, rref, sref,
+                      lp.data_ptr(), g_.data_ptr(), 1 if i == n - 1 else 0)
+
+    def _book(self, fr):
+        self.seq_no += 1
+        with torch.cuda.stream(self.side):
+            _lib.call("bjx_nuts_spec_book", _lib.current_stream(), fr.dref, self.rref, self.sref, self.seq_no,
+                      self.TIMEOUT_US)
+
+    def advance(self, fr):
+        """-> leapfrogs issued on stream A"""
+        # the bookkeeper of a sequence is launched BEFORE the sequence: replaying a recorded sequence keeps the host
+        # busy for about as long as the GPU needs to run it (every node is enqueued by the host), so a bookkeeper
+        # launched behind the replay started a whole sequence late (measured: a ring of lag, 26-56 wasted
+        # leapfrogs per transition end instead of 3-4)
+        if self.graph is not None:
+            for _ in range(self.reps):
+                self._book(fr)
+                self.graph.replay()
+            return self.seq * self.reps
+        n0 = self.SEQ0 if fr.can_record else self.seq
+        self._book(fr)
+        self._seq_a(fr, n0)
+        if fr.can_record:
+            self.graph = fr.record(self._seq_a, fr, self.seq)
+        return n0
+
+    def poll(self, fr):
+        with torch.cuda.stream(self.side):  # the finished-chain counter is stream B's
+            return fr.count.read()
+
+    def finish(self, fr):
+        torch.cuda.current_stream(fr.dev).wait_stream(self.side)
+        d = [int(v) for v in self.dbg.tolist()]
+        pushed = int(self.iw[:, 5].sum().item())
+        _SPEC_STATS.update(rows=self.cap, pushed=pushed, mismatches=d[0], stalls=d[1], restarts=d[2], stale=d[3],
+                           timeouts=d[4], out_of_order=d[5], sequences=self.seq_no,
+                           seconds=time.perf_counter() - self.t_enter,
+                           book_us_per_record=(d[6] / 100.0 / d[7]) if d[7] else None, book_records=d[7])
+        if d[0] or d[5]:
+            raise RuntimeError(f"speculative NUTS tail: the bookkeeper's replica disagreed with the integrator "
+                               f"({d[0]} position mismatches, {d[5]} out-of-order records) -- results discarded")
+
+
+class _FreeRun:
+    """One ``run_free`` run: its inputs, the device buffers its descriptors point to -- each an attribute of this
+    object or of a tail it owns, since the kernels reach them through raw pointers -- and the phases of the run.  The
+    phase objects (``_Batch``, ``_Tail``, ``_SpecTail``) take the run as an argument and keep no reference to it: a run
+    is then no reference cycle, and its buffers go back to the allocator as soon as its last reference goes (at the
+    end of a per-call run, at the eviction of a persistent workspace), not at some later cyclic collection.
+
+    ``capacity`` (``key_layout="step"`` / ``"step_major"``, a plain key, no adaptation / fuse_target / dense_gemm) makes
+    the run PERSISTENT: the per-call inputs (state, key, step size, metric) are copied into static buffers, so the
+    recorded tail sequences survive the call and ``rerun`` repeats the run without any allocation or recording.  The
+    recorded launches carry ``n_steps`` by value, so a ``step_major`` run of T <= capacity transitions starts every
+    chain's counter at t0 = capacity - T and uses rows t0 .. capacity - 1 of the key table and of the output arrays
+    (the kernels index both by the chain's absolute counter: csrc/bjx_nuts_tick_dev.h, async_ctx and the transition
+    end).  Results of a persistent run are clones."""
+
+    def __init__(self, rng_key, state: HMCState, logdensity_fn: Callable, step_size, inverse_mass_matrix,
+                 num_steps: int, max_num_doublings: int = 10, *, divergence_threshold: float = 1000,
+                 chain_offset: int = 0, key_layout: str = "step_major", store_positions: bool = True,
+                 sync_every=None, use_graph="auto", graph_max_rows: int = 8192, adaptation=None,
+                 fuse_target: bool = False, integrator=integrators.velocity_verlet, dense_gemm: bool = False,
+                 dense_gemm_cap=None, spec_rows=None, keep_ends: bool = False, capacity: Optional[int] = None):
+        self.q = check_batch(state.position, "state.position").clone()
+        self.logp = check_batch(state.logdensity, "state.logdensity").clone()
+        self.g = check_batch(state.logdensity_grad, "state.logdensity_grad").clone()
+        self.N, self.D = N, D = self.q.shape
+        self.dev = self.q.device
+        self.T = T = int(num_steps)
+        self.max_depth = int(max_num_doublings)
+        if self.max_depth < 1:
+            raise ValueError("free-running chains need max_num_doublings >= 1")
+        if key_layout not in ("step_major", "chain_major", "step"):
+            raise ValueError("key_layout must be 'step_major', 'chain_major' or 'step'")
+        if key_layout == "step" and T != 1:
+            raise ValueError("key_layout='step' is the single transition of step(): num_steps must be 1")
+        self.key_layout = key_layout
+        self.vg = value_and_grad(logdensity_fn)
+        self.persistent = capacity is not None
+        if self.persistent and (key_layout not in ("step", "step_major") or adaptation is not None or fuse_target
+                                or dense_gemm or bjx_random.key_spec(rng_key)[2] >= 0 or N == 0 or T == 0):
+            raise ValueError("a persistent free-running workspace serves key_layout='step' / 'step_major' with a plain key, "
+                             "without adaptation, fuse_target or dense_gemm")
+        self.capacity = max(T, int(capacity)) if self.persistent and key_layout == "step_major" else T
+        self._inputs(step_size, inverse_mass_matrix, adaptation, integrator, fuse_target, dense_gemm)
+        self.info = _run_info(self.capacity, N, self.dev, self.out_step_size)
+        self.positions = torch.empty((self.capacity, N, D), dtype=torch.float32, device=self.dev) if store_positions else None
+        self.batch = self.tail = self.spec = None  # the phase the run is in: busy batch, one-stream or speculative tail
+        self.kept_tail = self.kept_spec = None  # persistent run: the tails (and their recorded sequences) of earlier calls
+        self.empty = T == 0 or N == 0
+        if self.empty:
+            return
+        self._buffers(rng_key, dense_gemm_cap)
+        self._descriptors(divergence_threshold, chain_offset, keep_ends, fuse_target, logdensity_fn)
+        self._switches(sync_every, use_graph, graph_max_rows, spec_rows, logdensity_fn)
+
+    def _inputs(self, step_size, inverse_mass_matrix, adaptation, integrator, fuse_target, dense_gemm):
+        """Adaptation buffers, metric, integrator and step size: validated, and -- persistent run -- copied."""
+        N, D, T, dev = self.N, self.D, self.T, self.dev
+        self.adaptation, self.adapt_fields, self.out_step_size = adaptation, {}, None
+        if adaptation is not None:
+            ad = adaptation
+            for name, shape in (("log_x", (N,)), ("log_x_avg", (N,)), ("avg_err", (N,)), ("mu", (N,)),
+                                ("step_size", (N,)), ("mean", (N, D)), ("m2", (N, D)), ("imm", (N, D))):
+                b = ad[name]
+                if not (isinstance(b, torch.Tensor) and b.is_cuda and b.dtype == torch.float32
+                        and tuple(b.shape) == shape and b.is_contiguous()):
+                    raise ValueError(f"adaptation['{name}'] must be a contiguous float32 device tensor of shape {shape}")
+            tab_host = np.ascontiguousarray(ad["tab"], dtype=np.float32)
+            if tab_host.shape != (T, _lib.NUTS_ADAPT_COLS):
+                raise ValueError(f"adaptation['tab'] must have shape ({T}, {_lib.NUTS_ADAPT_COLS})")
+            self.adapt_tab = torch.as_tensor(tab_host, device=dev)
+            self.out_step_size = torch.empty((T, N), dtype=torch.float32, device=dev)
+            step_size, inverse_mass_matrix = ad["step_size"], metrics.PerChainDiag(ad["imm"])
+            self.adapt_fields = dict(
+                adapt_tab=self.adapt_tab.data_ptr(), adapt_target=float(ad["target"]), adapt_reserved=0.0,
+                adapt_log_x=ad["log_x"].data_ptr(), adapt_log_x_avg=ad["log_x_avg"].data_ptr(),
+                adapt_avg_err=ad["avg_err"].data_ptr(), adapt_mu=ad["mu"].data_ptr(),
+                adapt_step_size=ad["step_size"].data_ptr(), adapt_mean=ad["mean"].data_ptr(),
+                adapt_m2=ad["m2"].data_ptr(), adapt_imm=ad["imm"].data_ptr(),
+                out_step_size=self.out_step_size.data_ptr())
+        metric = metrics.default_metric(inverse_mass_matrix, N, D, dev)
+        integrators.check_supported(integrator, allow_general=True)
+        self.general = integrator is not integrators.velocity_verlet
+        self.kick_c, self.drift_c = integrator.coefficients[0::2], integrator.coefficients[1::2]
+        if self.general and (fuse_target or not free_running_supports(integrator, metric.kind, D)):
+            raise NotImplementedError(
+                f"free-running ticks with a multi-stage integrator: at most {_lib.NUTS_MAX_MID + 1} gradients per leapfrog "
+                "and no fuse_target")
+        if metric.kind != "diag" and adaptation is not None:
+            raise NotImplementedError("free-running per-chain adaptation is implemented for the diagonal metric")
+        self.gemm = bool(dense_gemm)
+        if self.gemm and (metric.kind != "dense" or self.general or fuse_target):
+            raise NotImplementedError("dense_gemm=True: one shared dense inverse mass matrix, velocity Verlet, no fuse_target")
+        eps, eps_pc = step_size_args(step_size, N, dev)
+        if self.persistent:  # static copies: recorded launches carry the descriptors by value
+            eps_buf = torch.empty(N, dtype=torch.float32, device=dev)
+            eps_buf.fill_(eps) if eps_pc is None else eps_buf.copy_(eps_pc)
+            metric = metric._replace(imm=metric.imm.clone())
+            eps, eps_pc = 0.0, eps_buf
+        if adaptation is not None and (eps_pc is None or eps_pc.data_ptr() != adaptation["step_size"].data_ptr()
+                                       or metric.imm.data_ptr() != adaptation["imm"].data_ptr()
+                                       or metric.imm_stride != D):
+            raise RuntimeError("adaptation buffers were copied on the way to the kernels")
+        self.metric, self.eps, self.eps_pc = metric, eps, eps_pc
+
+    def _buffers(self, rng_key, dense_gemm_cap):
+        """The key table, the tree state and the chain and work arrays of the tick kernels."""
+        N, D, T, Tc, dev, q, metric = self.N, self.D, self.T, self.capacity, self.dev, self.q, self.metric
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        self.step_keys, self.t_first, self.k0, self.k1 = None, 0, 0, 0
+        if self.key_layout == "step_major":
+            keys = bjx_random.split(rng_key, T)
+            self.step_keys = torch.zeros((Tc, 2), **i32)
+            self.step_keys[Tc - T:].copy_(torch.as_tensor(np.ascontiguousarray(keys).view(np.int32).reshape(T, 2)))
+        elif self.key_layout == "step":
+            k0, k1, fold = bjx_random.key_spec(rng_key)
+            if fold < 0:  # a plain key: the transition's own key; a ChainMajorKey: (run key, transition index)
+                self.step_keys = torch.as_tensor(np.array([[k0, k1]], dtype=np.uint32).view(np.int32), device=dev)
+            else:
+                self.k0, self.k1, self.t_first = k0, k1, int(fold)
+        else:
+            self.k0, self.k1 = bjx_random.key_words(rng_key)
+        self.tree, self.tree_fields = _tree_buffers(N, D, self.max_depth, dev, zero_ints=True)
+        self.p = torch.empty_like(q)
+        self.qf = torch.zeros_like(q)
+        self.t_done = torch.full((N,), Tc - T, **i32)
+        self.phase = torch.zeros(N, **i32)
+        # work buffers of the low-traffic tick kernels (include/bjx_nuts.h: rec / front_p; diagonal metric)
+        self.dense = _dense_fields(metric.kind, metric.imm, N, D, self.max_depth, dev)
+        self.v0 = None
+        if metric.kind != "diag":  # the tick kernel draws p = L^{-T} z and v0 = M^{-1} p per chain
+            self.v0 = torch.empty_like(q)
+            self.dense["fields"]["v0"] = self.v0.data_ptr()
+        if self.gemm:
+            # compact kicked momenta / their velocities (one GEMM per product), and the momentum list of a tick
+            cap = dense_gemm_cap if dense_gemm_cap is not None else _DENSE_GEMM_CAP
+            cap = int(cap) if cap and int(cap) > 0 else max(128, -(-N // 4))
+            self.gemm_cap = cap = min(N, -(-cap // 128) * 128)
+            self.gemm_bufs = (torch.zeros_like(q), torch.zeros_like(q), torch.zeros((cap, D), **f32),
+                              torch.zeros((cap, D), **f32), torch.zeros((cap, D), **f32))  # pc, vc, z, pm, vm
+            self.gemm_mass_sqrt = metric.mass_sqrt_t.t().contiguous()  # L^{-T} row-major: read as stored by the TN GEMM kernel
+            self.dense["fields"]["v_pre"] = self.gemm_bufs[1].data_ptr()
+        self.rec = torch.zeros((N, _lib.NUTS_REC_WORDS), **i32) if self.v0 is None else None
+        self.front_p = torch.empty_like(q) if self.v0 is None else None
+        self.end_list = torch.empty((2, N), **i32)
+        self.end_count = torch.zeros(2, **i32)
+        self.n_done = torch.zeros(1, **i32)
+
+    def _descriptors(self, divergence_threshold, chain_offset, keep_ends, fuse_target, logdensity_fn):
+        """``NutsDesc`` (the tree kernels' view) and the ``NutsAsync`` template every batch of rows copies."""
+        N, D, metric, info, general = self.N, self.D, self.metric, self.info, self.general
+        self.desc = _lib.NutsDesc(
+            N=N, D=D, max_depth=self.max_depth, reserved=0, imm=metric.imm.data_ptr(),
+            imm_stride=metric.imm_stride, eps_per_chain=_lib.ptr(self.eps_pc), eps=self.eps,
+            divergence_threshold=float(divergence_threshold), key0=self.k0, key1=self.k1,
+            chain_offset=int(chain_offset), step_fold=-1, q0=self.q.data_ptr(), g0=self.g.data_ptr(),
+            p0=self.p.data_ptr(), **self.tree_fields, **self.dense["fields"],
+            int_kick=self.kick_c[0] if general else 0.0, int_drift=self.drift_c[0] if general else 0.0)
+        a = self.async_desc = _lib.NutsAsync(
+            step_keys=_lib.ptr(self.step_keys), t_first=self.t_first, n_steps=self.capacity, q=self.q.data_ptr(),
+            g=self.g.data_ptr(), logp=self.logp.data_ptr(), p=self.p.data_ptr(), t=self.t_done.data_ptr(),
+            phase=self.phase.data_ptr(), n_done=self.n_done.data_ptr(), rows=None, n_rows=N,
+            out_position=_lib.ptr(self.positions),
+            out_logdensity=info.logdensity.data_ptr(), out_acceptance_rate=info.acceptance_rate.data_ptr(),
+            out_energy=info.energy.data_ptr(),
+            out_num_integration_steps=info.num_integration_steps.data_ptr(),
+            out_num_trajectory_expansions=info.num_trajectory_expansions.data_ptr(),
+            out_is_divergent=info.is_divergent.data_ptr(), out_is_turning=info.is_turning.data_ptr(),
+            rec=_lib.ptr(self.rec), front_p=_lib.ptr(self.front_p), end_list=self.end_list.data_ptr(),
+            end_count=self.end_count.data_ptr(),
+            mass_sqrt_t=_lib.ptr(metric.mass_sqrt_t if self.v0 is not None else None),
+            v0=_lib.ptr(self.v0), **self.adapt_fields)
+        if keep_ends:
+            if self.rec is None or fuse_target or D % 4 != 0 or D > 1024:
+                raise NotImplementedError("keep_ends is served by the lean tick kernels: diagonal metric, D % 4 == 0, D <= 1024, "
+                                          "external callable")
+            a.keep_ends = 1
+        if self.gemm:
+            (a.gemm_pc, a.gemm_vc, a.gemm_z, a.gemm_pm, a.gemm_vm) = (b.data_ptr() for b in self.gemm_bufs)
+            a.gemm_cap = self.gemm_cap
+            a.gemm_mass_sqrt = self.gemm_mass_sqrt.data_ptr()  # both matrices read as stored (bjx_dense_matmul_bt / apply_imm_t)
+            a.gemm_imm_t = metric.imm_t.data_ptr()
+        if general and len(self.drift_c) > 1:  # middle stages (b_2, a_2), ..., (b_K, a_K); the closing kick b_1 is int_kick
+            a.int_stages = len(self.drift_c)
+            for i in range(1, len(self.drift_c)):
+                a.int_mid_kick[i - 1], a.int_mid_drift[i - 1] = self.kick_c[i], self.drift_c[i]
+        self.fused, self.rtc_module = False, None
+        # with an engine-resident target a whole chunk of ticks is ONE launch (k_nuts_async_multi) at every batch size:
+        # measured at C3 (NOTEBOOK.md section 7) 322 / 340 / 220 M/s at T = 20 / 100 / 400 against 190 / 212 / 112 with
+        # one launch per tick -- the one-tick target kernels were removed in round 5
+        if fuse_target:
+            spec = getattr(logdensity_fn, "_bjx_fused_target", None)
+            spec = spec(D) if callable(spec) else None
+            if spec is None or metric.kind != "diag" or D % 4 != 0 or D > 512 or self.rec is None:
+                raise NotImplementedError(
+                    "fuse_target=True needs a blackjax_amd.targets log-density the tick kernels can evaluate "
+                    "(NealFunnel; DiagGaussian with D > 128), a diagonal metric, D % 4 == 0 and D <= 512")
+            if spec[0] == "rtc":
+                # a user-written device target (targets.DeviceTarget): the multi-tick kernel of csrc/bjx_nuts_tick_dev.h is
+                # compiled around it by hiprtc (blackjax_amd/rtc.py) and launched through the module API; every
+                # chunk of ticks is one launch (the library's one-tick kernels do not know the target)
+                self.rtc_module = spec[1].nuts_module()
+                a.target_kind, a.target_vec = _lib.NUTS_TARGET_USER, spec[1]._params_ptr(self.dev) or None
+            else:
+                a.target_kind, a.target_vec = int(spec[0]), _lib.ptr(spec[1])
+            self.fused_target = spec[1]  # the parameter vector, or the device target that owns it and the module
+            self.fused = True
+        self.dref = ctypes.byref(self.desc)
+        self.stream = _lib.current_stream()
+
+    def _switches(self, sync_every, use_graph, graph_max_rows, spec_rows, logdensity_fn):
+        """Scheduling switches (read once per call; a persistent run keeps them) and what the phases share."""
+        i32 = dict(dtype=torch.int32, device=self.dev)
+        if sync_every is None:
+            sync_every = 128 if self.fused else 16
+        sync_every = int(os.environ.get("BJX_NUTS_SYNC_EVERY", sync_every))
+        self.sync_every = max(2, sync_every + (sync_every & 1))  # even (GEMM mode alternates its momentum lists per tick)
+        self.graph_max_rows = int(os.environ.get("BJX_NUTS_TAIL_ROWS", graph_max_rows))
+        if use_graph not in (True, False, "auto"):
+            raise ValueError("use_graph must be True, False or 'auto'")
+        self.use_graph = use_graph
+        self.can_record = use_graph is True or (use_graph == "auto" and is_capturable(logdensity_fn))
+        if use_graph == "auto" and not self.can_record:
+            warn_eager_driver(logdensity_fn, "nuts.run")
+        self.src_work = torch.empty(self.N, **i32)
+        self.n_out = torch.zeros(1, **i32)
+        self.spec_rows = int(os.environ.get("BJX_NUTS_SPEC_ROWS", 128 if spec_rows is None else spec_rows))
+        # leapfrogs per recorded sequence of stream A (32 / 64 / 128 measured within 4 % of each other)
+        self.spec_seq = int(os.environ.get("BJX_NUTS_SPEC_SEQ", 64))
+        # sequences queued per host poll (round 6: 1 -- the host learns of the run's end one batch late, and a batch of
+        # 128 leapfrogs past the end cost `step` 4 % at C3)
+        self.spec_reps = int(os.environ.get("BJX_NUTS_SPEC_REPS", 1))
+        spec_ok = (self.spec_rows > 0 and self.can_record and self.rec is not None and not self.fused and not self.gemm
+                   and self.adaptation is None and not (self.general and len(self.drift_c) > 1) and self.D % 4 == 0
+                   and self.D <= 1024 and self.max_depth <= 30)
+        self.side_stream = _concurrent_side_stream(self.dev) if spec_ok else None  # probed once per (device, stream), then cached
+        self.spec_ok = spec_ok and self.side_stream is not None
+        self.lag_busy = os.environ.get("BJX_NUTS_LAG_BUSY", "1") != "0"
+        self.count = _LaggedCount(self.n_done)
+
+    def make_run(self, rows, n_rows):
+        """A copy of the ``NutsAsync`` template over the row list ``rows`` (``None``: row b is chain b)."""
+        r = _lib.NutsAsync()
+        ctypes.memmove(ctypes.byref(r), ctypes.byref(self.async_desc), ctypes.sizeof(self.async_desc))
+        r.rows, r.n_rows = _lib.ptr(rows), n_rows
+        return r
+
+    def multi_tick(self, run_k, qf_t, lp_t, g_t):
+        """One launch = ``run_k.ticks_per_launch`` ticks of every row of ``run_k`` (engine-resident target)."""
+        if self.rtc_module is None:
+            _lib.call("bjx_nuts_async_tick", _lib.current_stream(), self.dref, ctypes.byref(run_k), qf_t.data_ptr(),
+                      lp_t.data_ptr(), g_t.data_ptr())
+        elif run_k.n_rows > 0:
+            from . import rtc
+
+            self.rtc_module.launch(rtc.nuts_kernel_name(self.D), min(int(run_k.n_rows), 1 << 20), 64,
+                                   _lib.current_stream(), self.desc, run_k, ctypes.c_void_p(qf_t.data_ptr()),
+                                   ctypes.c_void_p(lp_t.data_ptr()), ctypes.c_void_p(g_t.data_ptr()))
+
+    def compact(self, src_rref, src_qf, rows, qf, count):
+        """The live rows of a batch (between two ticks) -> row list ``rows`` and pending positions ``qf``; their
+        number -> ``count`` (device)."""
+        _lib.call("bjx_nuts_async_compact", self.stream, self.dref, src_rref, src_qf.data_ptr(), rows.data_ptr(),
+                  qf.data_ptr(), self.src_work.data_ptr(), count.data_ptr())
+
+    def record(self, body, *args):
+        """A graph of the launches of ``body(*args)``.  Should the recording fail: ``use_graph=True`` re-raises, "auto"
+        takes it that the callable cannot be captured -- plain launches for the rest of the run -- and returns None."""
+        try:
+            cg = new_graph()
+            with record_graph(cg):
+                body(*args)
+            return cg
+        except Exception:
+            if self.use_graph is True:
+                raise
+            self.can_record = False
+            torch.cuda.synchronize()
+            return None
+
+    def _ticks_bound(self):
+        # K ticks per leaf; + one tick per transition: the busy-phase leaf kernel finishes a transition in the
+        # tick AFTER the one that completed its tree (deferred transition ends, k_nuts_async_tick3<.., DEFER>)
+        T = self.T
+        bound = T * (((1 << self.max_depth) - 1) * max(1, len(self.drift_c) if self.general else 1) + 1) + 4
+        if self.gemm:
+            # a chain may wait for a slot of the momentum list.  Slots are handed out by atomicAdd in arbitrary order and
+            # a waiting chain competes again in the next tick, so ceil(N / cap) - 1 ticks per start is the EXPECTED wait,
+            # not a strict bound (ADVICE r4): twice that plus a constant, so that a starved chain cannot trip the "did not
+            # finish within its tick bound" error spuriously (the bound only exists to stop a runaway loop)
+            bound += 2 * T * (-(-self.N // self.gemm_cap)) + 64
+        return bound
+
+    def run(self):
+        """The run on this object's buffers.  Should it raise while the second stream of a speculative tail still has
+        work queued, wait for the device before the buffers can go back to the allocator."""
+        if self.empty:
+            return self._result()
+        try:
+            return self._execute()
+        except BaseException:
+            if self.spec is not None:
+                try:
+                    torch.cuda.synchronize(self.dev)
+                except Exception:
+                    pass
+            raise
+
+    def rerun(self, rng_key, state, step_size, inverse_mass_matrix, num_steps=None):
+        """One more run of a persistent workspace: new key, state, step size and metric (``step_major`` workspaces: and
+        any number of transitions up to the capacity); no allocation, no recording."""
+        N, D, Tc = self.N, self.D, self.capacity
+        k0, k1, fold = bjx_random.key_spec(rng_key)
+        m2 = metrics.default_metric(inverse_mass_matrix, N, D, self.dev)
+        if fold >= 0 or m2.kind != self.metric.kind or tuple(m2.imm.shape) != tuple(self.metric.imm.shape):
+            raise ValueError("persistent free-running workspace: the key kind or the metric's shape changed")
+        T = self.T if num_steps is None else int(num_steps)
+        if not 1 <= T <= Tc or (self.key_layout == "step" and T != 1):
+            raise ValueError(f"persistent free-running workspace: {T} transitions asked of a capacity of {Tc}")
+        self.T = T
+        self.q.copy_(check_batch(state.position, "state.position"))
+        self.logp.copy_(check_batch(state.logdensity, "state.logdensity"))
+        self.g.copy_(check_batch(state.logdensity_grad, "state.logdensity_grad"))
+        eps, eps_pc = step_size_args(step_size, N, self.dev)
+        self.eps_pc.fill_(eps) if eps_pc is None else self.eps_pc.copy_(eps_pc)
+        self.metric.imm.copy_(m2.imm)
+        if self.key_layout == "step":
+            # the key's two words as integer fills (no host-to-device copy, hence no host synchronisation)
+            self.step_keys[0, 0].fill_(int(np.uint32(k0).astype(np.int32)))
+            self.step_keys[0, 1].fill_(int(np.uint32(k1).astype(np.int32)))
+        else:
+            keys = np.ascontiguousarray(bjx_random.split(rng_key, T)).view(np.int32).reshape(T, 2)
+            self.step_keys[Tc - T:].copy_(torch.as_tensor(keys))
+        for b in (self.phase, self.n_done, self.rec):
+            b.zero_()
+        self.t_done.fill_(Tc - T)
+        return self.run()
+
+    def _execute(self):
+        self._start()
+        while self.ticks_left > 0:
+            if self.spec is not None:
+                finished = self._spec_chunk()
+            elif self.tail is not None:
+                finished = self._tail_chunk()
+            else:
+                finished = self._busy_chunk()
+            if finished:
+                break
+        else:
+            if self.spec is not None:
+                torch.cuda.current_stream(self.dev).wait_stream(self.spec.side)
+            if int(self.n_done.item()) != self.N:
+                raise RuntimeError("free-running NUTS did not finish within its tick bound")
+        if self.spec is not None:
+            self.spec.finish(self)
+        self.batch = None
+        return self._result()
+
+    def _start(self):
+        """Set-up of a run: its tick bound, the live-count schedule, and every row in one busy batch."""
+        self.max_ticks = self._ticks_bound()
+        # ONE transition from a common start (`step`): every chain with d doublings ends at tick 2^d + 1 (start, 2^d - 1
+        # leaves, deferred end), so the live count only changes there -- the host looks right behind those ticks and compacts
+        # once at most 70 % of a batch is live.  Measured at C3 (tools/step_vs_run1.py, same call): 7.2 ms per transition
+        # against 7.9 with the schedule of a long run (a look every 16 ticks, compaction at one half) and 7.4 with a look
+        # every 8 ticks.  Runs of many transitions keep the old schedule: their chains desynchronise within a transition.
+        self.cohort_plan, self.compact_frac = None, 0.5
+        if self.T == 1 and not self.fused and not self.gemm:
+            self.cohort_plan, self.compact_frac = [(1 << d) + 1 for d in range(4, self.max_depth + 1)], 0.7
+        # ONE batch of all rows: Infinity-Cache-sized row groups were SLOWER at C3 (one group 138.6 M/s, groups of 16 384 /
+        # 8 192 / 4 096 rows 124.6 / 114.2 / 88.9 M/s, NOTEBOOK.md section 7), and two half-size groups on two concurrent
+        # streams gained nothing (round 6: 276 vs 279 M/s at T = 100)
+        self.batch = _Batch(self, None, self.N, self.qf)
+        self.tail = self.spec = None
+        self.ticks_left = self.max_ticks
+        self.count.reset(0)
+        _SPEC_STATS.clear()
+
+    def _busy_chunk(self):
+        """One chunk of ticks of the busy batch and the live count after it; few live rows: hand over to a tail, or
+        compact the batch (-> True once every chain has finished)."""
+        b, N = self.batch, self.N
+        tail = b.n_rows <= self.graph_max_rows
+        n_ticks = self.sync_every * (4 if tail else 1)
+        if self.cohort_plan is not None:  # one transition: look at the batch where a cohort of trees has just ended
+            done_ticks = self.max_ticks - self.ticks_left
+            n_ticks = next((e - done_ticks for e in self.cohort_plan if e > done_ticks), n_ticks)
+        # a batch that is small from the start (a run that STARTS with few chains) is recorded once its size has lasted
+        # 4 plain chunks
+        b.advance(self, n_ticks, self.can_record and self.ticks_left < self.max_ticks
+                  and (self.use_graph is True or (tail and b.eager_chunks >= 4)))
+        self.ticks_left -= n_ticks
+        if self.lag_busy and b.n_rows > self.graph_max_rows and self.cohort_plan is None:
+            # busy phase of a long run: the count of the PREVIOUS chunk (read behind this chunk's launches, so the
+            # GPU never drains while the host waits); it only grows, so a stale value delays a compaction by one
+            # chunk at most, and the exact count is read before anything is sized by it
+            n_active = N - self.count.read()
+            if n_active <= int(b.n_rows * self.compact_frac):
+                n_active = N - int(self.n_done.item())
+        else:
+            n_active = N - int(self.n_done.item())  # one host sync per chunk
+            self.count.reset(N - n_active)
+        if n_active == 0:
+            return True
+        if self.spec_ok and n_active <= self.spec_rows:
+            self._to_spec(b.rref, b.qf, n_active)  # few live chains: every tick is pure latency from here on
+        elif n_active <= int(b.n_rows * self.compact_frac) and b.n_rows > 64:
+            # drop the finished chains from the batch (device-side compaction + gather)
+            if self.can_record and n_active <= self.graph_max_rows:
+                self._to_tail(n_active)
+            else:
+                self._compact_batch(n_active)
+        return False
+
+    def _compact_batch(self, n_active):
+        """The live rows of the busy batch -> a new busy batch of ``n_active`` rows."""
+        old = self.batch
+        rows = torch.empty(old.n_rows, dtype=torch.int32, device=self.dev)
+        qf = torch.empty((old.n_rows, self.D), dtype=torch.float32, device=self.dev)
+        self.compact(old.rref, old.qf, rows, qf, self.n_out)
+        b = self.batch = _Batch(self, rows[:n_active], n_active, qf[:n_active])
+        b.logp_f, b.gf = eval_logdensity(self.vg, b.qf)  # the gathered positions, row for row
+
+    def _to_tail(self, n_active):
+        """The live rows of the busy batch -> the one-stream tail."""
+        if self.persistent:  # fixed capacity: one recording per tier serves every call
+            if self.kept_tail is None:
+                self.kept_tail = _Tail(self, min(self.N, self.graph_max_rows))
+            self.tail = self.kept_tail
+        else:
+            self.tail = _Tail(self, n_active)
+        self.tail.enter(self, self.batch, n_active)
+        self.count.reset(self.N - n_active)
+        self.batch = None
+
+    def _tail_chunk(self):
+        """A batch of the one-stream tail's sequences and the lagged live count after it (-> True once every chain
+        has finished)."""
+        tail = self.tail
+        if self.spec_ok and tail.n_cur <= self.spec_rows:
+            self._to_spec(ctypes.byref(tail.run[tail.cur]), tail.qf[tail.cur], tail.n_cur)
+            return False
+        self.ticks_left -= tail.advance(self)
+        n_active = self.N - self.count.read()
+        if n_active == 0:
+            return True
+        if self.spec_ok and n_active <= self.spec_rows:
+            tail.n_cur = n_active  # (an upper bound: the count is read one batch late)
+        elif tail.tier(n_active) < tail.view:
+            tail.compact(self, n_active)
+        return False
+
+    def _to_spec(self, src_rref, src_qf, n_live):
+        """The live rows of the busy batch or of the one-stream tail -> the speculative tail."""
+        if self.persistent:  # fixed capacity: one recording serves every call
+            if self.kept_spec is None:
+                self.kept_spec = _SpecTail(self, max(1, min(self.N, self.spec_rows)))
+            self.spec = self.kept_spec
+            self.spec.dbg.zero_()
+            self.spec.t_enter = time.perf_counter()
+        else:
+            self.spec = _SpecTail(self, max(1, n_live))
+        self.spec.enter(self, src_rref, src_qf)
+        self.batch = self.tail = None
+        self.count.last = max(self.count.last, self.N - n_live)
+        self.ticks_left += self.ticks_left // 2 + 4096  # leapfrogs speculated past transition ends, ring stalls
+
+    def _spec_chunk(self):
+        """A batch of the speculative tail's sequences (-> True once every chain has finished)."""
+        self.ticks_left -= self.spec.advance(self)
+        return self.spec.poll(self) == self.N
+
+    def _result(self):
+        """``(final_state, positions, info)``; a persistent run returns clones (its buffers serve the next call)."""
+        if not self.persistent:
+            return HMCState(self.q, self.logp, self.g), self.positions, self.info
+        t0 = self.capacity - self.T
+        state = HMCState(self.q.clone(), self.logp.clone(), self.g.clone())
+        out = [None if t is None else t[t0:].clone() for t in (self.positions, *self.info)]
+        return state, out[0], NUTSRunInfo(*out[1:])
+
+
 def run_free(rng_key, state: HMCState, logdensity_fn: Callable, step_size, inverse_mass_matrix,
              num_steps: int, max_num_doublings: int = 10, *, divergence_threshold: float = 1000,
              chain_offset: int = 0, key_layout: str = "step_major", store_positions: bool = True,
              sync_every=None, use_graph="auto", graph_max_rows: int = 8192, adaptation=None,
-             row_block=None, fuse_target: bool = False, integrator=integrators.velocity_verlet,
-             dense_gemm: bool = False, dense_gemm_cap=None, spec_rows=None, keep_ends: bool = False,
-             _handle: Optional[dict] = None):
+             fuse_target: bool = False, integrator=integrators.velocity_verlet,
+             dense_gemm: bool = False, dense_gemm_cap=None, spec_rows=None, keep_ends: bool = False):
     """``num_steps`` NUTS transitions of every chain WITHOUT lockstep (include/bjx_nuts.h,
     "free-running chains"): per tick each chain integrates one leapfrog of its own current tree and
     a chain that completes a transition starts its next one at once, so the user callable always
@@ -620,792 +1382,18 @@ def run_free(rng_key, state: HMCState, logdensity_fn: Callable, step_size, inver
     its LAST transition's trajectory in the work arrays (``bjx_nuts_async_t.keep_ends``) -- what ``step`` needs for
     ``NUTSInfo.trajectory_leftmost_state`` / ``rightmost_state``.
 
-    ``_handle`` (private; ``key_layout="step"``, a plain key, no adaptation / fuse_target / dense_gemm): a dict that makes
-    the call PERSISTENT -- every buffer is owned by the workspace and the per-call inputs (state, key, step size,
-    metric) are copied into static buffers, so the recorded tail sequences survive the call; the dict then holds
-    ``rerun(rng_key, state, step_size, inverse_mass_matrix)``, which repeats the run on the same workspace without
-    any allocation or recording, and ``work`` (the arrays ``keep_ends`` fills).  Results of a persistent call are clones.
-
     Returns ``(final_state, positions, info)``: ``positions`` is ``(num_steps, N, D)`` (``None`` when
     ``store_positions=False``), ``info`` a ``NUTSRunInfo``."""
-    import numpy as np
-
-    from . import random as bjx_random
-
-    q = check_batch(state.position, "state.position").clone()
-    logp = check_batch(state.logdensity, "state.logdensity").clone()
-    g = check_batch(state.logdensity_grad, "state.logdensity_grad").clone()
-    N, D = q.shape
-    dev = q.device
-    T = int(num_steps)
-    max_depth = int(max_num_doublings)
-    if max_depth < 1:
-        raise ValueError("free-running chains need max_num_doublings >= 1")
-    if key_layout not in ("step_major", "chain_major", "step"):
-        raise ValueError("key_layout must be 'step_major', 'chain_major' or 'step'")
-    if key_layout == "step" and T != 1:
-        raise ValueError("key_layout='step' is the single transition of step(): num_steps must be 1")
-    vg = value_and_grad(logdensity_fn)
-    f32 = dict(dtype=torch.float32, device=dev)
-    i32 = dict(dtype=torch.int32, device=dev)
-    persistent = _handle is not None
-    if persistent and (key_layout not in ("step", "step_major") or adaptation is not None or fuse_target or dense_gemm
-                       or bjx_random.key_spec(rng_key)[2] >= 0 or N == 0 or T == 0):
-        raise ValueError("a persistent free-running workspace serves key_layout='step' / 'step_major' with a plain key, "
-                         "without adaptation, fuse_target or dense_gemm")
-    # A persistent ``step_major`` workspace is built for a CAPACITY of transitions (``_handle["capacity"]`` >= T): the
-    # recorded launches carry ``n_steps`` by value, so a call of T <= capacity transitions starts every chain's counter at
-    # t0 = capacity - T and uses rows t0 .. capacity - 1 of the key table and of the output arrays (the kernels index
-    # both by the chain's absolute counter: csrc/bjx_nuts_tick_dev.h, async_ctx and the transition end)
-    Tc = T
-    if persistent and key_layout == "step_major":
-        Tc = max(T, int(_handle.get("capacity", T)))
-    cur = {"T": T, "t0": Tc - T}
-    adapt_fields = {}
-    out_step_size = None
-    if adaptation is not None:
-        ad = adaptation
-        for name, shape in (("log_x", (N,)), ("log_x_avg", (N,)), ("avg_err", (N,)), ("mu", (N,)),
-                            ("step_size", (N,)), ("mean", (N, D)), ("m2", (N, D)), ("imm", (N, D))):
-            b = ad[name]
-            if not (isinstance(b, torch.Tensor) and b.is_cuda and b.dtype == torch.float32
-                    and tuple(b.shape) == shape and b.is_contiguous()):
-                raise ValueError(f"adaptation['{name}'] must be a contiguous float32 device tensor of shape {shape}")
-        tab_host = np.ascontiguousarray(ad["tab"], dtype=np.float32)
-        if tab_host.shape != (T, _lib.NUTS_ADAPT_COLS):
-            raise ValueError(f"adaptation['tab'] must have shape ({T}, {_lib.NUTS_ADAPT_COLS})")
-        adapt_tab = torch.as_tensor(tab_host, device=dev)
-        out_step_size = torch.empty((T, N), **f32)
-        step_size, inverse_mass_matrix = ad["step_size"], metrics.PerChainDiag(ad["imm"])
-        adapt_fields = dict(
-            adapt_tab=adapt_tab.data_ptr(), adapt_target=float(ad["target"]), adapt_reserved=0.0,
-            adapt_log_x=ad["log_x"].data_ptr(), adapt_log_x_avg=ad["log_x_avg"].data_ptr(),
-            adapt_avg_err=ad["avg_err"].data_ptr(), adapt_mu=ad["mu"].data_ptr(),
-            adapt_step_size=ad["step_size"].data_ptr(), adapt_mean=ad["mean"].data_ptr(),
-            adapt_m2=ad["m2"].data_ptr(), adapt_imm=ad["imm"].data_ptr(),
-            out_step_size=out_step_size.data_ptr())
-    metric = metrics.default_metric(inverse_mass_matrix, N, D, dev)
-    integrators.check_supported(integrator, allow_general=True)
-    general = integrator is not integrators.velocity_verlet
-    kick_c, drift_c = integrator.coefficients[0::2], integrator.coefficients[1::2]
-    if general and (fuse_target or not free_running_supports(integrator, metric.kind, D)):
-        raise NotImplementedError(
-            f"free-running ticks with a multi-stage integrator: at most {_lib.NUTS_MAX_MID + 1} gradients per leapfrog "
-            "and no fuse_target")
-    if metric.kind != "diag" and adaptation is not None:
-        raise NotImplementedError("free-running per-chain adaptation is implemented for the diagonal metric")
-    gemm = bool(dense_gemm)
-    if gemm and (metric.kind != "dense" or general or fuse_target):
-        raise NotImplementedError("dense_gemm=True: one shared dense inverse mass matrix, velocity Verlet, no fuse_target")
-    eps, eps_pc = step_size_args(step_size, N, dev)
-    eps_buf = imm_buf = None
-    if persistent:  # static copies: recorded launches carry the descriptors by value
-        eps_buf = torch.empty(N, **f32)
-        eps_buf.fill_(eps) if eps_pc is None else eps_buf.copy_(eps_pc)
-        imm_buf = metric.imm.clone()
-        metric = metric._replace(imm=imm_buf)
-        eps, eps_pc = 0.0, eps_buf
-    if adaptation is not None and (eps_pc is None or eps_pc.data_ptr() != adaptation["step_size"].data_ptr()
-                                   or metric.imm.data_ptr() != adaptation["imm"].data_ptr()
-                                   or metric.imm_stride != D):
-        raise RuntimeError("adaptation buffers were copied on the way to the kernels")
-    info = NUTSRunInfo(torch.empty((Tc, N), **f32), torch.empty((Tc, N), **f32), torch.empty((Tc, N), **f32),
-                       torch.empty((Tc, N), **i32), torch.empty((Tc, N), **i32),
-                       torch.empty((Tc, N), dtype=torch.bool, device=dev),
-                       torch.empty((Tc, N), dtype=torch.bool, device=dev), out_step_size)
-    positions = torch.empty((Tc, N, D), **f32) if store_positions else None
-    if T == 0 or N == 0:
-        return HMCState(q, logp, g), positions, info
-
-    t_first = 0
-    if key_layout == "step_major":
-        keys = bjx_random.split(rng_key, T)
-        step_keys = torch.zeros((Tc, 2), **i32)
-        step_keys[Tc - T:].copy_(torch.as_tensor(np.ascontiguousarray(keys).view(np.int32).reshape(T, 2)))
-        k0 = k1 = 0
-    elif key_layout == "step":
-        k0, k1, fold = bjx_random.key_spec(rng_key)
-        step_keys = None
-        if fold < 0:  # a plain key: the transition's own key; a ChainMajorKey: (run key, transition index)
-            step_keys = torch.as_tensor(np.array([[k0, k1]], dtype=np.uint32).view(np.int32), device=dev)
-            k0 = k1 = 0
-        else:
-            t_first = int(fold)
-    else:
-        step_keys = None
-        k0, k1 = bjx_random.key_words(rng_key)
-    bufs = {n: torch.empty_like(q) for n in _BUFS}
-    ck_r = torch.empty((N, max_depth, D), **f32)
-    ck_rs = torch.empty_like(ck_r)
-    fs = torch.empty((_lib.NUTS_NF, N), **f32)
-    is_ = torch.zeros((_lib.NUTS_NI, N), **i32)
-    p = torch.empty_like(q)
-    qf = torch.zeros_like(q)
-    t_done = torch.full((N,), Tc - T, **i32)
-    phase = torch.zeros(N, **i32)
-    # work buffers of the low-traffic tick kernels (include/bjx_nuts.h: rec / front_p; diagonal metric)
-    dense_f = _dense_fields(metric.kind, metric.imm, N, D, max_depth, dev)
-    v0 = None
-    if metric.kind != "diag":  # the tick kernel draws p = L^{-T} z and v0 = M^{-1} p per chain
-        v0 = torch.empty_like(q)
-        dense_f["fields"]["v0"] = v0.data_ptr()
-    gemm_bufs = None
-    if gemm:
-        # compact kicked momenta / their velocities (one GEMM per product), and the momentum list of a tick
-        cap = dense_gemm_cap if dense_gemm_cap is not None else _DENSE_GEMM_CAP
-        cap = int(cap) if cap and int(cap) > 0 else max(128, -(-N // 4))
-        cap = min(N, -(-cap // 128) * 128)
-        gemm_bufs = (torch.zeros_like(q), torch.zeros_like(q), torch.zeros((cap, D), **f32),
-                     torch.zeros((cap, D), **f32), torch.zeros((cap, D), **f32), cap,
-                     metric.mass_sqrt_t.t().contiguous())  # L^{-T} row-major: read as stored by the TN GEMM kernel
-        dense_f["fields"]["v_pre"] = gemm_bufs[1].data_ptr()
-    rec = torch.zeros((N, _lib.NUTS_REC_WORDS), **i32) if v0 is None else None
-    front_p = torch.empty_like(q) if v0 is None else None
-    end_list = torch.empty((2, N), **i32)
-    end_count = torch.zeros(2, **i32)
-    n_done = torch.zeros(1, **i32)
-    desc = _lib.NutsDesc(
-        N=N, D=D, max_depth=max_depth, reserved=0, imm=metric.imm.data_ptr(),
-        imm_stride=metric.imm_stride, eps_per_chain=_lib.ptr(eps_pc), eps=eps,
-        divergence_threshold=float(divergence_threshold), key0=k0, key1=k1,
-        chain_offset=int(chain_offset), step_fold=-1, q0=q.data_ptr(), g0=g.data_ptr(),
-        p0=p.data_ptr(), ckpt_r=ck_r.data_ptr(), ckpt_rs=ck_rs.data_ptr(), fs=fs.data_ptr(),
-        is_=is_.data_ptr(), **{n: b.data_ptr() for n, b in bufs.items()}, **dense_f["fields"],
-        int_kick=kick_c[0] if general else 0.0, int_drift=drift_c[0] if general else 0.0)
-    run = _lib.NutsAsync(
-        step_keys=_lib.ptr(step_keys), t_first=t_first, n_steps=Tc, q=q.data_ptr(), g=g.data_ptr(),
-        logp=logp.data_ptr(), p=p.data_ptr(), t=t_done.data_ptr(), phase=phase.data_ptr(),
-        n_done=n_done.data_ptr(), rows=None, n_rows=N, out_position=_lib.ptr(positions),
-        out_logdensity=info.logdensity.data_ptr(), out_acceptance_rate=info.acceptance_rate.data_ptr(),
-        out_energy=info.energy.data_ptr(),
-        out_num_integration_steps=info.num_integration_steps.data_ptr(),
-        out_num_trajectory_expansions=info.num_trajectory_expansions.data_ptr(),
-        out_is_divergent=info.is_divergent.data_ptr(), out_is_turning=info.is_turning.data_ptr(),
-        rec=_lib.ptr(rec), front_p=_lib.ptr(front_p), end_list=end_list.data_ptr(),
-        end_count=end_count.data_ptr(), mass_sqrt_t=_lib.ptr(metric.mass_sqrt_t if v0 is not None else None),
-        v0=_lib.ptr(v0), **adapt_fields)
-    if keep_ends:
-        if rec is None or fuse_target or D % 4 != 0 or D > 1024:
-            raise NotImplementedError("keep_ends is served by the lean tick kernels: diagonal metric, D % 4 == 0, D <= 1024, "
-                                      "external callable")
-        run.keep_ends = 1
-    if gemm_bufs is not None:
-        (run.gemm_pc, run.gemm_vc, run.gemm_z, run.gemm_pm, run.gemm_vm) = (b.data_ptr() for b in gemm_bufs[:5])
-        run.gemm_cap = gemm_bufs[5]
-        run.gemm_mass_sqrt = gemm_bufs[6].data_ptr()  # both matrices read as stored (bjx_dense_matmul_bt / apply_imm_t)
-        run.gemm_imm_t = metric.imm_t.data_ptr()
-    if general and len(drift_c) > 1:  # middle stages (b_2, a_2), ..., (b_K, a_K); the closing kick b_1 is int_kick
-        run.int_stages = len(drift_c)
-        for i in range(1, len(drift_c)):
-            run.int_mid_kick[i - 1], run.int_mid_drift[i - 1] = kick_c[i], drift_c[i]
-    fused = False
-    rtc_module = None
-    # with an engine-resident target a whole chunk of ticks is ONE launch (k_nuts_async_multi) at every batch size:
-    # measured at C3 (NOTEBOOK.md section 7) 322 / 340 / 220 M/s at T = 20 / 100 / 400 against 190 / 212 / 112 with
-    # one launch per tick -- the one-tick target kernels were removed in round 5
-    if fuse_target:
-        spec = getattr(logdensity_fn, "_bjx_fused_target", None)
-        spec = spec(D) if callable(spec) else None
-        if spec is None or metric.kind != "diag" or D % 4 != 0 or D > 512 or rec is None:
-            raise NotImplementedError(
-                "fuse_target=True needs a blackjax_amd.targets log-density the tick kernels can evaluate "
-                "(NealFunnel; DiagGaussian with D > 128), a diagonal metric, D % 4 == 0 and D <= 512")
-        if spec[0] == "rtc":
-            # a user-written device target (targets.DeviceTarget): the multi-tick kernel of csrc/bjx_nuts_tick_dev.h is
-            # compiled around it by hiprtc (blackjax_amd/rtc.py) and launched through the module API; every
-            # chunk of ticks is one launch (the library's one-tick kernels do not know the target)
-            rtc_target = spec[1]
-            rtc_module = rtc_target.nuts_module()
-            run.target_kind, run.target_vec = _lib.NUTS_TARGET_USER, rtc_target._params_ptr(dev) or None
-        else:
-            run.target_kind, run.target_vec = int(spec[0]), _lib.ptr(spec[1])
-        fused_keep = spec[1]  # noqa: F841  (keeps the parameter vector / the compiled module alive for the run)
-        fused = True
-    dref, rref = ctypes.byref(desc), ctypes.byref(run)
-    stream = _lib.current_stream()
-    # K ticks per leaf; + one tick per transition: the busy-phase leaf kernel finishes a transition in the
-    # tick AFTER the one that completed its tree (deferred transition ends, k_nuts_async_tick3<.., DEFER>)
-    def ticks_bound(T_):
-        b_ = T_ * (((1 << max_depth) - 1) * max(1, len(drift_c) if general else 1) + 1) + 4
-        if gemm_bufs is not None:
-            # a chain may wait for a slot of the momentum list.  Slots are handed out by atomicAdd in arbitrary order and
-            # a waiting chain competes again in the next tick, so ceil(N / cap) - 1 ticks per start is the EXPECTED wait,
-            # not a strict bound (ADVICE r4): twice that plus a constant, so that a starved chain cannot trip the "did not
-            # finish within its tick bound" error spuriously (the bound only exists to stop a runaway loop)
-            b_ += 2 * T_ * (-(-N // gemm_bufs[5])) + 64
-        return b_
-
-    max_ticks = ticks_bound(T)
-    if sync_every is None:
-        sync_every = 128 if fused else 16
-    sync_every = int(_os_environ().get("BJX_NUTS_SYNC_EVERY", sync_every))
-    sync_every = max(2, int(sync_every) + (int(sync_every) & 1))  # even (GEMM mode alternates its momentum lists per tick)
-    import os as _os
-
-    graph_max_rows = int(_os.environ.get("BJX_NUTS_TAIL_ROWS", graph_max_rows))
-    if use_graph not in (True, False, "auto"):
-        raise ValueError("use_graph must be True, False or 'auto'")
-    can_record = use_graph is True or (use_graph == "auto" and is_capturable(logdensity_fn))
-    if use_graph == "auto" and not can_record:
-        warn_eager_driver(logdensity_fn, "nuts.run")
-
-    def multi_tick(run_k, qf_t, lp_t, g_t):
-        """One launch = ``run_k.ticks_per_launch`` ticks of every row of ``run_k`` (engine-resident target)."""
-        if rtc_module is None:
-            _lib.call("bjx_nuts_async_tick", _lib.current_stream(), dref, ctypes.byref(run_k), qf_t.data_ptr(),
-                      lp_t.data_ptr(), g_t.data_ptr())
-        elif run_k.n_rows > 0:
-            from . import rtc
-
-            rtc_module.launch(rtc.nuts_kernel_name(D), min(int(run_k.n_rows), 1 << 20), 64, _lib.current_stream(),
-                              desc, run_k, ctypes.c_void_p(qf_t.data_ptr()), ctypes.c_void_p(lp_t.data_ptr()),
-                              ctypes.c_void_p(g_t.data_ptr()))
-
-    def make_run(rows, n_rows):
-        r = _lib.NutsAsync()
-        ctypes.memmove(ctypes.byref(r), ctypes.byref(run), ctypes.sizeof(run))  # copy of the template
-        r.rows, r.n_rows = _lib.ptr(rows), n_rows
-        return r
-
-    class _Group:
-        """A set of compact rows ticked together: (qf, logp_f, gf) batch + its row list."""
-
-        def __init__(self, rows, n_rows, qf_g):
-            self.rows, self.n_rows, self.qf = rows, n_rows, qf_g
-            self.run = make_run(rows, n_rows)
-            self.rref = ctypes.byref(self.run)
-            self.logp_f = torch.zeros(n_rows, **f32)  # the first tick only starts transitions
-            self.gf = torch.zeros_like(qf_g)
-            self.graph = None  # (CUDAGraph, static logp_f, static gf, n_ticks)
-            self.eager_chunks = 0
-
-        def chunk(self, n_ticks, logp_f, gf):
-            """``n_ticks`` ticks, each followed by the callable on the group's batch."""
-            if fused:
-                # engine-resident target + one-launch ticks: the whole chunk is ONE launch, every wave
-                # advancing its chain n_ticks times (bjx_nuts_async_t.ticks_per_launch)
-                self.run.tick, self.run.ticks_per_launch = 0, n_ticks
-                multi_tick(self.run, self.qf, logp_f, gf)
-                return logp_f, gf
-            for i in range(n_ticks):
-                self.run.tick = i & 1
-                _lib.call("bjx_nuts_async_tick", _lib.current_stream(), dref, self.rref, self.qf.data_ptr(),
-                          logp_f.data_ptr(), gf.data_ptr())
-                logp_f, gf = eval_logdensity(vg, self.qf)
-            return logp_f, gf
-
-        def advance(self, n_ticks, record):
-            nonlocal can_record
-            if self.graph is not None and self.graph[3] == n_ticks:
-                self.graph[0].replay()
-                return
-            self.graph = None
-            self.logp_f, self.gf = self.chunk(n_ticks, self.logp_f, self.gf)
-            self.eager_chunks += 1
-            if record:
-                # recording does not execute anything, so the chains' state is untouched by it
-                lp_s, g_s = self.logp_f.clone(), self.gf.clone()
-                try:
-                    cg = new_graph()
-                    with record_graph(cg):
-                        lp_e, g_e = self.chunk(n_ticks, lp_s, g_s)
-                        if lp_e is not lp_s:
-                            lp_s.copy_(lp_e)
-                            g_s.copy_(g_e)
-                    self.graph = (cg, lp_s, g_s, n_ticks)
-                    self.logp_f, self.gf = lp_s, g_s
-                except Exception:
-                    if use_graph is True:
-                        raise
-                    can_record = False  # "auto": this callable cannot be captured -- plain launches
-                    torch.cuda.synchronize()
-
-    src_work = torch.empty(N, **i32)
-    n_out = torch.zeros(1, **i32)
-
-    class _Tail:
-        """The tail of a run (at most ``cap`` live rows) on FIXED-CAPACITY buffers: the kernels read
-        the live-row count from device memory (``n_rows_dev``, include/bjx_nuts.h), so ONE recorded
-        chunk of ticks per (buffer set, view size) serves every batch size in between -- compaction
-        only rewrites the row list, the pending positions and the count.  Two buffer sets because a
-        compaction cannot work in place.
-
-        Round 3: the launch geometry and the callable's batch follow TIERS of the live-row count
-        (``cap``, then 4 096, 2 048, 512, 128, 32 rows: prefix views of the same buffers, one recording each) instead
-        of staying at ``cap`` to the end: with three live chains the callable used to be evaluated on
-        all ``cap`` rows every tick.  Round 6: ``cap`` is up to 8 192 rows (2 048 before) -- between 2 048 and 8 192 live
-        rows a tick is 16-20 us of GPU work and plain launches from Python took 33 us (NOTEBOOK section 19).  Rows of a view beyond the live count always hold a
-        VALID position (the buffers start as copies of a current chain state and are only ever
-        overwritten with pending positions), so a log-density that validates its support never sees
-        zeros or garbage there."""
-
-        TIERS = (32, 128, 512, 2048, 4096)
-
-        def __init__(self, cap, n_ticks, reps):
-            # a recorded sequence of n_ticks ticks, replayed `reps` times per host sync: recording
-            # costs ~40 us per tick, so a short sequence pays for itself within a few hundred ticks
-            self.cap, self.n_ticks, self.reps = cap, n_ticks, reps
-            self.tiered = True  # tail sequences follow tiers of the live-row count (cap / 512 / 128 / 32 rows)
-            self.rows = [torch.zeros(cap, **i32) for _ in range(2)]
-            # valid positions everywhere.  repeat(), not expand().contiguous(): with cap == 1 the latter IS q[:1] (already
-            # contiguous, no copy), and the last live chain's pending positions were then written into chain 0's state
-            # row (round 5: found by the row-width sweep of tests/test_nuts_v3_gpu.py; latent since round 3)
-            self.qf = [q[:1].repeat(cap, 1) for _ in range(2)]
-            self.n_dev = [torch.zeros(1, **i32) for _ in range(2)]
-            self.run = []
-            for k in range(2):
-                r = make_run(self.rows[k], cap)
-                r.n_rows_dev = self.n_dev[k].data_ptr()
-                self.run.append(r)
-            self.graph = {}   # (buffer set, view rows) -> (CUDAGraph, ticks per replay)
-            self.cur, self.n_cur, self.view = 0, 0, cap
-            if fused:  # in/out (logp, grad) of the pending positions, one pair per buffer set
-                self.lp = [torch.zeros(cap, **f32) for _ in range(2)]
-                self.g = [torch.zeros((cap, D), **f32) for _ in range(2)]
-
-        def tier(self, n_active):
-            if not self.tiered:
-                return self.cap
-            for v in self.TIERS:
-                if n_active <= v and v < self.cap:
-                    return v
-            return self.cap
-
-        def _after_compaction(self, k, n_active):
-            self.view = self.tier(n_active)
-            self.run[k].n_rows = self.view
-            self.cur, self.n_cur = k, n_active
-            if fused:  # (logp, grad) of the gathered positions: one stand-alone evaluation, then in place
-                lp, g_ = eval_logdensity(vg, self.qf[k][:self.view])
-                self.lp[k][:self.view].copy_(lp)
-                self.g[k][:self.view].copy_(g_)
-
-        def chunk_ticks(self):
-            """Ticks per recorded sequence: the few-row tiers are pure launch latency (two dependent
-            kernels per tick), so their sequences are longer -- fewer replay boundaries per tick."""
-            mult = 4
-            return self.n_ticks * (mult if (self.tiered and self.view <= 128) else 1)
-
-        def enter(self, groups_in, n_active):
-            off = 0
-            for g_ in groups_in:
-                _lib.call("bjx_nuts_async_compact", stream, dref, g_.rref, g_.qf.data_ptr(),
-                          self.rows[0][off:].data_ptr(), self.qf[0][off:].data_ptr(), src_work.data_ptr(),
-                          n_out.data_ptr())
-                off += int(n_out.item()) if len(groups_in) > 1 else n_active
-            assert off == n_active, (off, n_active)
-            self.n_dev[0].fill_(n_active)
-            self._after_compaction(0, n_active)
-
-        def wants_compaction(self, n_active):
-            if self.tiered:
-                return self.tier(n_active) < self.view
-            return n_active <= self.n_cur // 2 and self.n_cur > 64
-
-        def compact(self, n_active):
-            x, y = self.cur, self.cur ^ 1
-            _lib.call("bjx_nuts_async_compact", stream, dref, ctypes.byref(self.run[x]), self.qf[x].data_ptr(),
-                      self.rows[y].data_ptr(), self.qf[y].data_ptr(), src_work.data_ptr(),
-                      self.n_dev[y].data_ptr())
-            self._after_compaction(y, n_active)
-
-        def _body(self, k, n_ticks):
-            """``n_ticks`` x (callable on the pending positions, tick).  CALLABLE FIRST: what carries
-            over from one sequence to the next is then ``qf`` alone -- a fixed buffer the last tick
-            wrote -- and a replay needs no copies of the callable's outputs into static inputs (round 2
-            copied logp and the gradient once per sequence: 0.85 us per tick in the deep tail)."""
-            qf_v = self.qf[k][:self.view]
-            rref_k = ctypes.byref(self.run[k])
-            if fused:
-                lp, g_ = self.lp[k][:self.view], self.g[k][:self.view]
-                self.run[k].tick, self.run[k].ticks_per_launch = 0, n_ticks  # the whole sequence as one launch
-                multi_tick(self.run[k], qf_v, lp, g_)
-                return
-            for i in range(n_ticks):
-                lp, g_ = eval_logdensity(vg, qf_v)
-                self.run[k].tick = i & 1
-                _lib.call("bjx_nuts_async_tick", _lib.current_stream(), dref, rref_k, qf_v.data_ptr(),
-                          lp.data_ptr(), g_.data_ptr())
-
-        def advance(self):
-            """-> ticks issued"""
-            nonlocal can_record
-            k = self.cur
-            hit = self.graph.get((k, self.view))
-            if hit is not None:
-                for _ in range(self.reps):
-                    hit[0].replay()
-                return hit[1] * self.reps
-            n = self.chunk_ticks()
-            self._body(k, self.n_ticks)  # one short plain sequence first (kernels, allocator warm)
-            issued = self.n_ticks
-            if can_record:
-                try:
-                    cg = new_graph()
-                    with record_graph(cg):
-                        self._body(k, n)
-                    self.graph[(k, self.view)] = (cg, n)
-                except Exception:
-                    if use_graph is True:
-                        raise
-                    can_record = False
-                    torch.cuda.synchronize()
-            return issued
-
-    spec_rows = int(_os.environ.get("BJX_NUTS_SPEC_ROWS", 128 if spec_rows is None else spec_rows))
-    spec_ok = (spec_rows > 0 and can_record and rec is not None and not fused and gemm_bufs is None
-               and adaptation is None and not (general and len(drift_c) > 1) and D % 4 == 0 and D <= 1024
-               and max_depth <= 30)
-    side_stream = _concurrent_side_stream(dev) if spec_ok else None  # probed once per (device, stream), then cached
-    spec_ok = spec_ok and side_stream is not None
-
-    class _SpecTail:
-        """The two-stream speculative tail (include/bjx_nuts.h): stream A = the current stream, [callable, integrate]
-        per leapfrog as one recorded sequence; stream B = ``side``, one long-lived bookkeeping launch per sequence."""
-
-        RING = 64      # ring slots per row
-        LEAD = 4       # records the integrator may run ahead of the bookkeeper's consumed count (2: stalls; 4 .. 63: flat at
-                       # D = 256, where a record costs the bookkeeper 3.2 us against 4.9 us per leaf on stream A)
-        SEQ = int(_os.environ.get("BJX_NUTS_SPEC_SEQ", 64))  # leapfrogs per recorded sequence of stream A (32 / 64 / 128 measured within 4 % of each other)
-        SEQ0 = 8       # plain leapfrogs before the recording (kernels, allocator warm)
-        REPS = int(_os.environ.get("BJX_NUTS_SPEC_REPS", 1))  # sequences queued per host poll (round 6: 1 -- the host learns of the
-                       # run's end one batch late, and a batch of 128 leapfrogs past the end cost `step` 4 % at C3)
-        TIMEOUT_US = 20000
-
-        def __init__(self, cap):
-            self.cap = cap
-            self.rows = torch.zeros(cap, **i32)
-            self.qf = q[:1].repeat(cap, 1)  # valid positions everywhere (see _Tail)
-            self.n_dev = torch.zeros(1, **i32)
-            mk = lambda: torch.zeros((cap, D), **f32)  # noqa: E731
-            self.fp, self.qf_book = mk(), mk()
-            self.ends = [mk() for _ in range(6)]
-            self.iw = torch.zeros((cap, _lib.NUTS_SPEC_IW), **i32)
-            self.bw = torch.zeros((cap, _lib.NUTS_SPEC_IW), **i32)
-            self.ring_g = torch.zeros((cap, self.RING, D), **f32)
-            self.ring_tag = torch.zeros((cap, self.RING, _lib.NUTS_SPEC_TAG), **i32)
-            self.avail = torch.zeros(cap, **i32)
-            self.ack = torch.zeros(cap, dtype=torch.int64, device=dev)
-            self.a_seq = torch.zeros(1, **i32)
-            self.dbg = torch.zeros(8, **i32)
-            self.run = make_run(self.rows, cap)
-            self.run.n_rows_dev = self.n_dev.data_ptr()
-            e = self.ends
-            self.spec = _lib.NutsSpec(
-                n_rows=cap, n_rows_dev=self.n_dev.data_ptr(), rows=self.rows.data_ptr(), ring=self.RING,
-                lead=self.LEAD,
-                qf=self.qf.data_ptr(), fp=self.fp.data_ptr(), eLq=e[0].data_ptr(), eLp=e[1].data_ptr(),
-                eLg=e[2].data_ptr(), eRq=e[3].data_ptr(), eRp=e[4].data_ptr(), eRg=e[5].data_ptr(),
-                iw=self.iw.data_ptr(), ring_g=self.ring_g.data_ptr(), ring_tag=self.ring_tag.data_ptr(),
-                avail=self.avail.data_ptr(), ack=self.ack.data_ptr(), qf_book=self.qf_book.data_ptr(), bw=self.bw.data_ptr(),
-                a_seq=self.a_seq.data_ptr(), dbg=self.dbg.data_ptr())
-            self.rref, self.sref = ctypes.byref(self.run), ctypes.byref(self.spec)
-            self.side = side_stream
-            self.graph = None
-            self.seq_no = 0
-            self.t_enter = __import__("time").perf_counter()
-
-        def enter(self, src_rref, src_qf):
-            """Live rows of the source batch (between two ticks) -> this tail."""
-            _lib.call("bjx_nuts_async_compact", stream, dref, src_rref, src_qf.data_ptr(), self.rows.data_ptr(),
-                      self.qf.data_ptr(), src_work.data_ptr(), self.n_dev.data_ptr())
-            _lib.call("bjx_nuts_spec_enter", stream, dref, self.rref, self.sref)
-            self.side.wait_stream(torch.cuda.current_stream(dev))
-
-        def _seq_a(self, n):
-            for i in range(n):
-                lp, g_ = eval_logdensity(vg, self.qf)
-                _lib.call("bjx_nuts_spec_integrate", _lib.current_stream(), dref, self.rref, self.sref,
-                          lp.data_ptr(), g_.data_ptr(), 1 if i == n - 1 else 0)
-
-        def _book(self):
-            self.seq_no += 1
-            with torch.cuda.stream(self.side):
-                _lib.call("bjx_nuts_spec_book", _lib.current_stream(), dref, self.rref, self.sref, self.seq_no,
-                          self.TIMEOUT_US)
-
-        def advance(self):
-            """-> leapfrogs issued on stream A"""
-            nonlocal can_record
-            # the bookkeeper of a sequence is launched BEFORE the sequence: replaying a recorded sequence keeps the host
-            # busy for about as long as the GPU needs to run it (every node is enqueued by the host), so a bookkeeper
-            # launched behind the replay started a whole sequence late (measured: a ring of lag, 26-56 wasted
-            # leapfrogs per transition end instead of 3-4)
-            if self.graph is not None:
-                for _ in range(self.REPS):
-                    self._book()
-                    self.graph.replay()
-                return self.SEQ * self.REPS
-            n0 = self.SEQ0 if can_record else self.SEQ
-            self._book()
-            self._seq_a(n0)
-            if can_record:
-                try:
-                    cg = new_graph()
-                    with record_graph(cg):
-                        self._seq_a(self.SEQ)
-                    self.graph = cg
-                except Exception:
-                    if use_graph is True:
-                        raise
-                    can_record = False
-                    torch.cuda.synchronize()
-            return n0
-
-        def poll(self):
-            with torch.cuda.stream(self.side):  # the finished-chain counter is stream B's
-                return poll_done()
-
-        def finish(self):
-            torch.cuda.current_stream(dev).wait_stream(self.side)
-            d = [int(v) for v in self.dbg.tolist()]
-            pushed = int(self.iw[:, 5].sum().item())
-            _SPEC_STATS.update(rows=self.cap, pushed=pushed, mismatches=d[0], stalls=d[1], restarts=d[2], stale=d[3],
-                               timeouts=d[4], out_of_order=d[5], sequences=self.seq_no,
-                               seconds=__import__("time").perf_counter() - self.t_enter,
-                               book_us_per_record=(d[6] / 100.0 / d[7]) if d[7] else None, book_records=d[7])
-            if d[0] or d[5]:
-                raise RuntimeError(f"speculative NUTS tail: the bookkeeper's replica disagreed with the integrator "
-                                   f"({d[0]} position mismatches, {d[5]} out-of-order records) -- results discarded")
-
-    # Lagged completion polling for the tail: the finished-chain count is copied to pinned host memory
-    # behind every batch of replays and the host reads the copy of the PREVIOUS batch, so the next
-    # batch is always queued before the host waits -- the GPU never idles on the round trip of a
-    # blocking .item() (0.5-1 us per tick of a 12 us tick).  The count only grows: a stale (smaller)
-    # value is safe for the tier choice, and the run ends at most one batch late (ticks over finished
-    # chains do nothing).
-    lag_busy = _os.environ.get("BJX_NUTS_LAG_BUSY", "1") != "0"
-    pinned = [torch.zeros(1, dtype=torch.int32).pin_memory() for _ in range(2)]
-    poll_ev = [torch.cuda.Event() for _ in range(2)]
-    poll = {"slot": 0, "primed": False, "last": 0}
-
-    def poll_done():
-        k = poll["slot"]
-        pinned[k].copy_(n_done, non_blocking=True)
-        poll_ev[k].record()
-        poll["slot"] = k ^ 1
-        if poll["primed"]:
-            poll_ev[k ^ 1].synchronize()
-            poll["last"] = int(pinned[k ^ 1][0])
-        poll["primed"] = True
-        return poll["last"]
-
-    groups: list = []
-    tail_ctx = spec_ctx = None
-    ticks_left = max_ticks
-    # ONE transition from a common start (`step`): every chain with d doublings ends at tick 2^d + 1 (start, 2^d - 1
-    # leaves, deferred end), so the live count only changes there -- the host looks right behind those ticks and compacts
-    # once at most 70 % of a batch is live.  Measured at C3 (tools/step_vs_run1.py, same call): 7.2 ms per transition
-    # against 7.9 with the schedule of a long run (a look every 16 ticks, compaction at one half) and 7.4 with a look
-    # every 8 ticks.  Runs of many transitions keep the old schedule: their chains desynchronise within a transition.
-    cohort_plan, compact_frac = None, 0.5
-    cohort_ok = not fused and gemm_bufs is None
-    static = {"tail": None, "spec": None}  # persistent workspace: the tails (and their recorded sequences) of earlier calls
-
-    def to_spec(src_rref, src_qf, n_live):
-        nonlocal spec_ctx, ticks_left
-        if persistent:  # fixed capacity: one recording serves every call
-            if static["spec"] is None:
-                static["spec"] = _SpecTail(max(1, min(N, spec_rows)))
-            spec_ctx = static["spec"]
-            spec_ctx.dbg.zero_()
-            spec_ctx.t_enter = __import__("time").perf_counter()
-        else:
-            spec_ctx = _SpecTail(max(1, n_live))
-        spec_ctx.enter(src_rref, src_qf)
-        poll["last"] = max(poll["last"], N - n_live)
-        ticks_left += ticks_left // 2 + 4096  # leapfrogs speculated past transition ends, ring stalls
-
-    def execute():
-        """The run itself, on the buffers set up above (a persistent workspace calls it once per transition)."""
-        nonlocal groups, tail_ctx, spec_ctx, ticks_left, max_ticks, cohort_plan, compact_frac
-        max_ticks = ticks_bound(cur["T"])
-        cohort_plan, compact_frac = None, 0.5
-        if cur["T"] == 1 and cohort_ok:
-            cohort_plan, compact_frac = [(1 << d_) + 1 for d_ in range(4, max_depth + 1)], 0.7
-        # Row groups: the ensemble may be ticked group by group, each advanced by a chunk of ticks before
-        # the next one gets its turn (chains are independent, so the results do not depend on the
-        # grouping).  One group by default -- see auto_row_block for the measurement.
-        rb = auto_row_block(N, D) if row_block is None else int(row_block)
-        blk = N if not rb or rb >= N else rb
-        groups = []
-        for s0 in range(0, N, blk):
-            n_g = min(blk, N - s0)
-            rows_g = None if blk >= N else torch.arange(s0, s0 + n_g, **i32)
-            groups.append(_Group(rows_g, n_g, qf[s0:s0 + n_g]))
-        tail_ctx = spec_ctx = None
-        ticks_left = max_ticks
-        poll.update(primed=False, last=0)
-        _SPEC_STATS.clear()
-        while ticks_left > 0:
-            if spec_ctx is not None:
-                ticks_left -= spec_ctx.advance()
-                if N - spec_ctx.poll() == 0:
-                    break
-                continue
-            if tail_ctx is not None:
-                if spec_ok and tail_ctx.n_cur <= spec_rows:
-                    to_spec(ctypes.byref(tail_ctx.run[tail_ctx.cur]), tail_ctx.qf[tail_ctx.cur], tail_ctx.n_cur)
-                    tail_ctx = None
-                    continue
-                ticks_left -= tail_ctx.advance()
-                n_active = N - poll_done()
-                if n_active == 0:
-                    break
-                if spec_ok and n_active <= spec_rows:
-                    tail_ctx.n_cur = n_active  # (an upper bound: the count is read one batch late)
-                    continue
-                if tail_ctx.wants_compaction(n_active):
-                    tail_ctx.compact(n_active)
-                continue
-            n_rows = sum(g_.n_rows for g_ in groups)
-            tail = n_rows <= graph_max_rows
-            n_ticks = sync_every * (4 if tail else 1)
-            if cohort_plan is not None:  # one transition: look at the batch where a cohort of trees has just ended
-                done_ticks = max_ticks - ticks_left
-                n_ticks = next((b_ - done_ticks for b_ in cohort_plan if b_ > done_ticks), n_ticks)
-            for g_ in groups:
-                # a multi-group schedule replays fixed-size groups for many chunks: record at once; a
-                # single small group (a run that STARTS with few chains) is recorded once its batch size
-                # has lasted 4 plain chunks
-                rec_now = can_record and ticks_left < max_ticks and (
-                    use_graph is True or len(groups) > 1 or (tail and g_.eager_chunks >= 4))
-                g_.advance(n_ticks, rec_now)
-            ticks_left -= n_ticks
-            if lag_busy and n_rows > graph_max_rows and cohort_plan is None:
-                # busy phase of a long run: the count of the PREVIOUS chunk (read behind this chunk's launches, so the
-                # GPU never drains while the host waits); it only grows, so a stale value delays a compaction by one
-                # chunk at most, and the exact count is read before anything is sized by it
-                n_active = N - poll_done()
-                if n_active <= int(n_rows * compact_frac):
-                    n_active = N - int(n_done.item())
-            else:
-                n_active = N - int(n_done.item())  # one host sync per chunk
-                poll.update(primed=False, last=N - n_active)
-            if n_active == 0:
-                break
-            if spec_ok and n_active <= spec_rows and len(groups) == 1:
-                to_spec(groups[0].rref, groups[0].qf, n_active)  # few live chains: every tick is pure latency from here on
-                groups = []
-                continue
-            if n_active <= int(n_rows * compact_frac) and n_rows > 64:
-                # drop the finished chains from the batch (device-side compaction + gather); the groups
-                # are merged into one batch of the live rows
-                if can_record and n_active <= graph_max_rows:
-                    if persistent:
-                        if static["tail"] is None:
-                            static["tail"] = _Tail(min(N, graph_max_rows), sync_every, 4)
-                        tail_ctx = static["tail"]
-                    else:
-                        tail_ctx = _Tail(n_active, sync_every, 4)
-                    tail_ctx.enter(groups, n_active)
-                    poll.update(primed=False, last=N - n_active)
-                    groups = []
-                    continue
-                rows_all = torch.empty(n_rows, **i32)
-                qf_all = torch.empty((n_rows, D), **f32)
-                off = 0
-                for g_ in groups:
-                    _lib.call("bjx_nuts_async_compact", stream, dref, g_.rref, g_.qf.data_ptr(),
-                              rows_all[off:].data_ptr(), qf_all[off:].data_ptr(), src_work.data_ptr(),
-                              n_out.data_ptr())
-                    off += int(n_out.item()) if len(groups) > 1 else n_active
-                assert off == n_active, (off, n_active)
-                rb = auto_row_block(n_active, D) if row_block is None else int(row_block)
-                blk_now = n_active if not rb or rb >= n_active else rb
-                groups = []
-                for s0 in range(0, n_active, blk_now):
-                    n_g = min(blk_now, n_active - s0)
-                    g_ = _Group(rows_all[s0:s0 + n_g], n_g, qf_all[s0:s0 + n_g])
-                    g_.logp_f, g_.gf = eval_logdensity(vg, g_.qf)  # the gathered positions, row for row
-                    groups.append(g_)
-        else:
-            if spec_ctx is not None:
-                torch.cuda.current_stream(dev).wait_stream(spec_ctx.side)
-            if int(n_done.item()) != N:
-                raise RuntimeError("free-running NUTS did not finish within its tick bound")
-        if spec_ctx is not None:
-            spec_ctx.finish()
-        groups = []
-        if persistent:  # the buffers are reused by the next call
-            c = lambda t: None if t is None else t[cur["t0"]:].clone()  # noqa: E731
-            return (HMCState(q.clone(), logp.clone(), g.clone()), c(positions),
-                    NUTSRunInfo(*[c(getattr(info, f)) for f in NUTSRunInfo._fields]))
-        return HMCState(q, logp, g), positions, info
-
-    def guarded():
-        """execute(); should it raise while the second stream of a speculative tail still has work queued, wait for the
-        device before the frame's buffers go back to the allocator."""
-        try:
-            return execute()
-        except BaseException:
-            if spec_ctx is not None:
-                try:
-                    torch.cuda.synchronize(dev)
-                except Exception:
-                    pass
-            raise
-
-    if not persistent:
-        return guarded()
-
-    kind0, imm_shape0 = metric.kind, tuple(imm_buf.shape)
-
-    def rerun(rng_key2, state2, step_size2, inverse_mass_matrix2, num_steps2=None):
-        """One more run on this workspace: new key, state, step size and metric (``step_major`` workspaces: and any
-        number of transitions up to the capacity); no allocation, no recording."""
-        k0_, k1_, fold_ = bjx_random.key_spec(rng_key2)
-        m2 = metrics.default_metric(inverse_mass_matrix2, N, D, dev)
-        if fold_ >= 0 or m2.kind != kind0 or tuple(m2.imm.shape) != imm_shape0:
-            raise ValueError("persistent free-running workspace: the key kind or the metric's shape changed")
-        T2 = cur["T"] if num_steps2 is None else int(num_steps2)
-        if not 1 <= T2 <= Tc or (key_layout == "step" and T2 != 1):
-            raise ValueError(f"persistent free-running workspace: {T2} transitions asked of a capacity of {Tc}")
-        cur.update(T=T2, t0=Tc - T2)
-        q.copy_(check_batch(state2.position, "state.position"))
-        logp.copy_(check_batch(state2.logdensity, "state.logdensity"))
-        g.copy_(check_batch(state2.logdensity_grad, "state.logdensity_grad"))
-        e2, epc2 = step_size_args(step_size2, N, dev)
-        eps_buf.fill_(e2) if epc2 is None else eps_buf.copy_(epc2)
-        imm_buf.copy_(m2.imm)
-        if key_layout == "step":
-            # the key's two words as integer fills (no host-to-device copy, hence no host synchronisation)
-            step_keys[0, 0].fill_(int(np.uint32(k0_).astype(np.int32)))
-            step_keys[0, 1].fill_(int(np.uint32(k1_).astype(np.int32)))
-        else:
-            keys2 = np.ascontiguousarray(bjx_random.split(rng_key2, T2)).view(np.int32).reshape(T2, 2)
-            step_keys[Tc - T2:].copy_(torch.as_tensor(keys2))
-        for b_ in (phase, n_done, rec):
-            b_.zero_()
-        t_done.fill_(Tc - T2)
-        return guarded()
-
-    _handle["rerun"] = rerun
-    _handle["capacity"] = Tc
-    _handle["work"] = {"p": p, "bufs": bufs, "rec": rec}
-    # EVERY device buffer the descriptors point to must outlive this call: the kernels of later reruns reach them through
-    # raw pointers, and a tensor that only this frame referenced (checkpoints, slot tables, the front momentum ...) would
-    # go back to the allocator on return -- and be handed to somebody else while the workspace still writes to it
-    # (found as box-independent but allocation-pattern-dependent wrong draws on the second call: NOTEBOOK.md section 16.8)
-    _handle["keep"] = [q, logp, g, p, qf, t_done, phase, n_done, rec, front_p, end_list, end_count, ck_r, ck_rs, fs, is_,
-                       step_keys, src_work, n_out, eps_buf, imm_buf, info, positions, bufs, dense_f, v0, gemm_bufs, metric]
-    return guarded()
+    return _FreeRun(**locals()).run()  # every argument by name (tests/test_static_names.py checks the two signatures)
 
 
 def _run_lockstep(step_fn, rng_key, state, num_steps, key_layout, store_positions):
     """``run`` through ``num_steps`` lockstep steps (same keys, same draws as ``run_free``)."""
-    from . import random as bjx_random
-
     T = int(num_steps)
     N, D = state.position.shape
     dev = state.position.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    i32 = dict(dtype=torch.int32, device=dev)
-    info = NUTSRunInfo(torch.empty((T, N), **f32), torch.empty((T, N), **f32), torch.empty((T, N), **f32),
-                       torch.empty((T, N), **i32), torch.empty((T, N), **i32),
-                       torch.empty((T, N), dtype=torch.bool, device=dev),
-                       torch.empty((T, N), dtype=torch.bool, device=dev), None)
-    positions = torch.empty((T, N, D), **f32) if store_positions else None
+    info = _run_info(T, N, dev)
+    positions = torch.empty((T, N, D), dtype=torch.float32, device=dev) if store_positions else None
     if key_layout not in ("step_major", "chain_major"):
         raise ValueError("key_layout must be 'step_major' or 'chain_major'")
     keys = bjx_random.split(rng_key, T) if key_layout == "step_major" else None
@@ -1455,10 +1443,10 @@ def as_top_level_api(logdensity_fn: Callable, step_size, inverse_mass_matrix, *,
     # chains during most of a transition; the free-running tick kernels with the two-stream speculative tail spend
     # 4.9 us instead of ~7-8 us on such a leaf, and give the same draws and the same NUTSInfo bit for bit
     # (tests/test_nuts_step_free_gpu.py).  What used to make this path lose -- buffers and tail recordings set up per
-    # call -- now happens once per (shape, callable, stream): run_free(_handle=...).
+    # call -- now happens once per (shape, callable, stream): a persistent _FreeRun.
     free_ws: dict = {}
     free_bad: set = set()
-    step_driver = _os_environ().get("BJX_NUTS_STEP_DRIVER", step_driver)
+    step_driver = os.environ.get("BJX_NUTS_STEP_DRIVER", step_driver)
 
     def _free_step_key(rng_key, state, for_run=False):
         if ((step_driver == "lockstep" and not for_run) or fuse_default or use_graph is False
@@ -1491,30 +1479,29 @@ def as_top_level_api(logdensity_fn: Callable, step_size, inverse_mass_matrix, *,
         torch.cuda.synchronize(state.position.device)
 
     def _free_step(wkey, rng_key, state):
-        h = free_ws.get(wkey)
+        fr = free_ws.get(wkey)
         try:
-            if h is None:
-                h = {}
-                new_state, _, ri = run_free(
+            if fr is None:
+                fr = _FreeRun(
                     rng_key, state, logdensity_fn, step_size, inverse_mass_matrix, 1, max_num_doublings,
                     divergence_threshold=divergence_threshold, chain_offset=chain_offset, key_layout="step",
                     store_positions=False, use_graph=True if use_graph is True else run_use_graph,
-                    integrator=integrator, keep_ends=True, spec_rows=step_spec_rows, _handle=h)
+                    integrator=integrator, keep_ends=True, spec_rows=step_spec_rows, capacity=1)
+                new_state, _, ri = fr.run()
                 while len(free_ws) >= 2:  # a workspace is ~20 (N, D) buffers: keep the two most recent shapes only
                     free_ws.pop(next(iter(free_ws)))
-                free_ws[wkey] = h
+                free_ws[wkey] = fr
             else:
-                new_state, _, ri = h["rerun"](rng_key, state, step_size, inverse_mass_matrix)
+                new_state, _, ri = fr.rerun(rng_key, state, step_size, inverse_mass_matrix)
         except RuntimeError as err:
             if step_driver == "free":
                 raise
             _free_step_failed(wkey, state, err)
             return None
-        w = h["work"]
-        b_, rec_f = w["bufs"], w["rec"].view(torch.float32)
+        b_, rec_f = fr.tree, fr.rec.view(torch.float32)
         c = lambda t: t.clone()  # noqa: E731
         info = NUTSInfo(
-            c(w["p"]), ri.is_divergent[0], ri.is_turning[0], ri.energy[0],
+            c(fr.p), ri.is_divergent[0], ri.is_turning[0], ri.energy[0],
             IntegratorState(c(b_["Lq"]), c(b_["Lp"]), c(rec_f[:, 29]), c(b_["Lg"])),
             IntegratorState(c(b_["Rq"]), c(b_["Rp"]), c(rec_f[:, 30]), c(b_["Rg"])),
             ri.num_trajectory_expansions[0], ri.num_integration_steps[0], ri.acceptance_rate[0])
@@ -1529,34 +1516,34 @@ def as_top_level_api(logdensity_fn: Callable, step_size, inverse_mass_matrix, *,
     RUN_WS_MAX_POSITION_BYTES = 2 << 30  # a workspace keeps its (capacity, N, D) position array: beyond this, per-call buffers
 
     def _run_ws_enabled():
-        return _os_environ().get("BJX_NUTS_RUN_WS", "1") != "0"
+        return os.environ.get("BJX_NUTS_RUN_WS", "1") != "0"
 
     def _persistent_run(wkey, rng_key, state, T, store_positions):
         if wkey in run_bad:
             return None
         n_, d_ = state.position.shape
-        h = run_ws.get(wkey)
-        if h is not None and h["capacity"] < T:
+        fr = run_ws.get(wkey)
+        if fr is not None and fr.capacity < T:
             run_ws.pop(wkey)
-            h = None
+            fr = None
         cap = T if store_positions else max(T, 512)  # (capacity, N) info arrays only: 22 B per chain and transition
-        if h is None and store_positions and cap * n_ * d_ * 4 > RUN_WS_MAX_POSITION_BYTES:
+        if fr is None and store_positions and cap * n_ * d_ * 4 > RUN_WS_MAX_POSITION_BYTES:
             return None
         try:
-            if h is None:
+            if fr is None:
                 # a workspace is ~20 (N, D) buffers + two checkpoint stacks: the two most recent are kept, one when they are large
                 ws_bytes = 4 * n_ * d_ * (20 + 2 * int(max_num_doublings))
                 while len(run_ws) >= (2 if ws_bytes < (4 << 30) else 1):
                     run_ws.pop(next(iter(run_ws)))
-                h = {"capacity": cap}
-                out = run_free(
+                fr = _FreeRun(
                     rng_key, state, logdensity_fn, step_size, inverse_mass_matrix, T, max_num_doublings,
                     divergence_threshold=divergence_threshold, chain_offset=chain_offset, key_layout="step_major",
                     store_positions=store_positions, use_graph=True if use_graph is True else run_use_graph,
-                    integrator=integrator, _handle=h)
-                run_ws[wkey] = h
+                    integrator=integrator, capacity=cap)
+                out = fr.run()
+                run_ws[wkey] = fr
                 return out
-            return h["rerun"](rng_key, state, step_size, inverse_mass_matrix, T)
+            return fr.rerun(rng_key, state, step_size, inverse_mass_matrix, T)
         except RuntimeError as err:
             # a recording failed or the speculative tail's replica check fired: the per-call driver restarts from `state`
             import warnings
@@ -1600,7 +1587,7 @@ def as_top_level_api(logdensity_fn: Callable, step_size, inverse_mass_matrix, *,
             # run is made of lockstep steps: same keys, run(T) == T x step bit for bit.  BJX_NUTS_FREE_GEMM=1
             # (velocity Verlet): free-running ticks with every product on the GEMM instead (bjx_nuts_async_t.gemm_*:
             # the same arithmetic, so the same results)
-            if not general and _os_environ().get("BJX_NUTS_FREE_GEMM", "0") != "0":
+            if not general and os.environ.get("BJX_NUTS_FREE_GEMM", "0") != "0":
                 return run_free(rng_key, state, logdensity_fn, step_size, inverse_mass_matrix, num_steps,
                                 max_num_doublings, divergence_threshold=divergence_threshold,
                                 chain_offset=chain_offset, key_layout=key_layout, store_positions=store_positions,

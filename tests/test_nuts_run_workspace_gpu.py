@@ -174,6 +174,53 @@ def test_run_workspaces_interleaved_on_streams_and_threads(dev):
         same(res[n], alone[n])
 
 
+def test_runs_and_evicted_workspaces_are_freed_by_reference_counting(dev, monkeypatch):
+    """A free-running run holds no reference cycle: with the cyclic collector off, the run object of a per-call
+    ``run_free`` (through either tail) is freed when the call returns, and a persistent ``step`` / ``run`` workspace as
+    soon as it is evicted (the drivers keep the two most recent shapes) -- its device buffers go back to the allocator at
+    once, not at some later full collection."""
+    import gc
+    import importlib
+    import weakref
+
+    bnuts = importlib.import_module("blackjax_amd.nuts")
+    made = []
+
+    class Probe(bnuts._FreeRun):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            made.append(weakref.ref(self))
+
+    monkeypatch.setattr(bnuts, "_FreeRun", Probe)
+    D = 32
+    fn = bjx.targets.NealFunnel()
+    imm = torch.ones(D, device=dev)
+    gen = torch.Generator(device=dev).manual_seed(9)
+    q = {n: 0.3 * torch.randn(n, D, device=dev, generator=gen) for n in (300, 200, 120)}
+    alg = bjx.nuts(fn, 0.2, imm, max_num_doublings=6)
+    gc.collect()
+    gc.disable()
+    monkeypatch.setattr(gc, "collect", lambda *a, **k: 0)  # torch.cuda.graph collects before every recording
+    try:
+        for spec_rows in (None, 0):  # busy phase -> speculative tail; -> one-stream tail
+            out = bnuts.run_free(bjx.random.key(1), alg.init(q[300]), fn, 0.2, imm, 3, 6, spec_rows=spec_rows)
+            del out
+            assert made[-1]() is None, f"a per-call run (spec_rows={spec_rows}) outlived its call"
+        first = len(made)
+        for n in (300, 200, 120):
+            st = alg.init(q[n])
+            alg.step(bjx.random.key(2), st)
+            alg.run(bjx.random.key(3), st, 2, store_positions=False)
+        ws = made[first:]  # step and run workspace of each shape, in order
+        assert len(ws) == 6
+        assert ws[0]() is None, "the evicted step workspace is still alive"
+        assert ws[1]() is None, "the evicted run workspace is still alive"
+        assert all(w() is not None for w in ws[2:])
+    finally:
+        monkeypatch.undo()
+        gc.enable()
+
+
 def test_run_workspace_per_chain_step_size_and_metric(dev, monkeypatch):
     """Per-chain step sizes and a per-chain diagonal metric (what window_adaptation hands to the sampler) go through the
     workspace's static copies; a multi-stage integrator runs on it too."""

@@ -34,3 +34,16 @@ def test_no_unresolved_names_in_package_and_bench():
     problems = {os.path.relpath(f, ROOT): _unresolved(f) for f in files}
     problems = {f: b for f, b in problems.items() if b}
     assert not problems, problems
+
+
+def test_run_free_signature_is_the_run_objects():
+    """``nuts.run_free`` hands its arguments to ``nuts._FreeRun`` by name, and the persistent workspaces construct
+    ``_FreeRun`` directly on its defaults: the two signatures must agree (``_FreeRun`` adds ``capacity`` only)."""
+    import importlib
+    import inspect
+
+    nuts = importlib.import_module("blackjax_amd.nuts")
+    front = inspect.signature(nuts.run_free).parameters
+    run = dict(inspect.signature(nuts._FreeRun.__init__).parameters)
+    del run["self"], run["capacity"]
+    assert [(p.name, p.kind, p.default) for p in front.values()] == [(p.name, p.kind, p.default) for p in run.values()]
