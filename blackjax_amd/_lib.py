@@ -115,6 +115,7 @@ SIGNATURES = {
     "bjx_welford_final_diag": [c_void_p, c_int64, c_int64, c_int64, c_float, _f32p, _f32p, c_int64,
                                _f32p],
     "bjx_target_diag_gaussian": [c_void_p, c_int64, c_int64, _f32p, _f32p, _f32p, _f32p],
+    "bjx_target_diag_gaussian_grad": [c_void_p, c_int64, c_int64, _f32p, _f32p, _f32p],
     "bjx_target_neal_funnel": [c_void_p, c_int64, c_int64, _f32p, _f32p, _f32p],
     "bjx_target_ar1_gaussian": [c_void_p, c_int64, c_int64, c_float, c_float, c_float, _f32p,
                                 _f32p, _f32p],

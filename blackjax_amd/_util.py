@@ -180,6 +180,33 @@ def value_and_grad(logdensity_fn: Callable) -> Callable:
         # autograd evaluation; anything it cannot express, or that fails the check, stays on autograd.
         return _autograd_or_elementwise(q, first=(out.detach(), g))
 
+    def _generated(q):
+        """The generated target to serve this call directly, or None: no target (yet) for this shape, or this call is
+        one of those re-checked against autograd -- ``vg(q)`` then serves it and does the full (logp, g) comparison.
+        Counts the call exactly as ``_autograd_or_elementwise`` does."""
+        if mode["kind"] != "autograd":
+            return None
+        key = (int(q.shape[-1]), q.device)
+        tgt = ew.get(key)
+        if tgt is None:
+            return None
+        n = calls.get(key, 0) + 1
+        if (n in _RECHECK_AT or n % _RECHECK_EVERY == 0) and not (q.is_cuda and torch.cuda.is_current_stream_capturing()):
+            return None
+        calls[key] = n
+        return tgt
+
+    def eval_into_(q, logp_out, g_out):
+        tgt = _generated(q)
+        return False if tgt is None else tgt._bjx_eval_into(q, logp_out, g_out)
+
+    def grad_into_(q, g_out):
+        tgt = _generated(q)
+        return False if tgt is None else tgt._bjx_grad_into(q, g_out)
+
+    if mode["kind"] != "pair":  # a declared (logp, grad) callable is never traced: nothing to forward
+        vg._bjx_eval_into = eval_into_
+        vg._bjx_grad_into = grad_into_
     vg._bjx_elementwise = ew
     vg._bjx_value_and_grad = True
     try:
@@ -363,6 +390,27 @@ def eval_logdensity(vg: Callable, q: torch.Tensor):
             f"{tuple(q.shape)}; got {tuple(logp.shape)} and {tuple(g.shape)}"
         )
     return logp.contiguous(), g.contiguous()
+
+
+def eval_into(vg: Callable, q: torch.Tensor, logp_out: torch.Tensor, g_out: torch.Tensor, need_logp: bool = True):
+    """``eval_logdensity`` for a driver that owns the output buffers.  A callable may offer two optional capabilities
+    (``blackjax_amd.targets`` do; a traced function does once its generated kernel exists):
+
+    * ``_bjx_eval_into(q, logp_out, g_out)``: evaluate into the caller's contiguous fp32 ``(n,)`` / ``(n, D)`` buffers;
+    * ``_bjx_grad_into(q, g_out)``: the gradient alone, used when ``need_logp`` is false (inside an HMC trajectory
+      with the endpoint proposal only the last evaluation's logp is read).
+
+    Either may return ``False`` to decline a call.  Returns ``(logp, g)``: ``g is g_out`` when the callable wrote into
+    the buffers (``logp`` is then ``logp_out``, or ``None`` for a gradient-only call); a callable without the
+    capabilities is called exactly as ``eval_logdensity`` calls it and its own outputs are returned."""
+    if not need_logp:
+        f = getattr(vg, "_bjx_grad_into", None)
+        if f is not None and f(q, g_out) is not False:
+            return None, g_out
+    f = getattr(vg, "_bjx_eval_into", None)
+    if f is not None and f(q, logp_out, g_out) is not False:
+        return logp_out, g_out
+    return eval_logdensity(vg, q)
 
 
 def step_size_args(step_size, n_chains: int, device):

@@ -68,6 +68,67 @@ k_diag_gaussian(int64_t N, int64_t D, const float* __restrict__ iv, const float*
   }
 }
 
+#ifndef BJX_REVERSE_ROWS
+#define BJX_REVERSE_ROWS 1  // bjx_hmc.hip: the flat leapfrog kernels number their workgroups from the end of the arrays
+#endif
+
+// The 256-piece span a workgroup of the flat gradient-only kernels works on.  Spans are taken in ascending order
+// (the leapfrog that follows sweeps last-to-first and starts on what was written last), but inside every aligned
+// group of eight workgroups the order is the LEAPFROG's: workgroup b runs on XCD b % 8, the flat leapfrog gives span
+// s to workgroup grid - 1 - s, so here span s goes to the workgroup of the same group with b % 8 == (grid - 1 - s) % 8.
+// A span's q is then read -- and its g written -- on the XCD whose (private, 4 MiB) L2 the leapfrog wrote it from and
+// will read it into: measured on 16 384 x 1 024 cache-resident pseudo-random rows (tools/lf_variants), leapfrog +
+// callable 67.2 -> 64.0 us per step against 66.9 us with plainly ascending workgroups; the kernel on its own does not
+// change (19.5 / 19.6 us).  A last group of fewer than eight workgroups keeps its numbering.
+__device__ __forceinline__ unsigned grad_span_of_workgroup() {
+  const unsigned b = blockIdx.x, G = gridDim.x;
+  if (!BJX_REVERSE_ROWS || (b | 7u) >= G) return b;
+  return (b & ~7u) + ((G - 1u - b) & 7u);
+}
+
+// Gradient only, g = -(q*inv_var): the fp32 expression of k_diag_gaussian, so the bits are the same.  Inside an
+// HMC trajectory with the endpoint proposal every evaluation but the last is made for its gradient; without the
+// fp64 row sum nothing is per row, so the launch takes the leapfrog's geometry (k_leapfrog_diag_flat): one 16-byte
+// piece per lane, one workgroup per 4 KB span of a row (D % 1024 == 0), no loop.  Workgroups ASCEND (first row
+// first, grad_span_of_workgroup): the leapfrog that follows sweeps last-to-first and finds the rows written last
+// still in cache.
+template <bool NT = false>
+__global__ void __launch_bounds__(kBlock)
+k_diag_gaussian_grad_flat(int64_t D, int bpr, const float* __restrict__ iv, const float* __restrict__ q,
+                          float* __restrict__ g) {
+  const unsigned b = grad_span_of_workgroup();
+  const int64_t r = b / (unsigned)bpr;
+  const int64_t j = (int64_t)(b - (unsigned)r * (unsigned)bpr) * 1024 + threadIdx.x * 4;
+  const int64_t at = r * D + j;
+  const F4 qq = ld4_t<NT>(q + at), vv = ld4(iv + j);
+  st4_t<NT>(g + at, F4{-(qq.x * vv.x), -(qq.y * vv.y), -(qq.z * vv.z), -(qq.w * vv.w)});
+}
+
+// any row length that is a multiple of 4 floats: lane i owns the i-th 16-byte piece of the (N, D) arrays
+// (k_leapfrog_diag_flat_any's indexing; the host checks N * D / 4 < 2^31)
+template <bool NT = false>
+__global__ void __launch_bounds__(kBlock)
+k_diag_gaussian_grad_flat_any(uint32_t total4, uint32_t D4, const float* __restrict__ iv,
+                              const float* __restrict__ q, float* __restrict__ g) {
+  const uint32_t i = grad_span_of_workgroup() * kBlock + threadIdx.x;
+  if (i >= total4) return;
+  const uint32_t j4 = i % D4;
+  const int64_t at = (int64_t)i * 4;
+  const F4 qq = ld4_t<NT>(q + at), vv = ld4(iv + (int64_t)j4 * 4);
+  st4_t<NT>(g + at, F4{-(qq.x * vv.x), -(qq.y * vv.y), -(qq.z * vv.z), -(qq.w * vv.w)});
+}
+
+// rows that are not a multiple of 4 floats (or unaligned buffers): one row per wave, 4 bytes per lane
+__global__ void __launch_bounds__(kBlock)
+k_diag_gaussian_grad_rows(int64_t N, int64_t D, const float* __restrict__ iv, const float* __restrict__ q,
+                          float* __restrict__ g) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t r = wave_row0(); r < N; r += wave_row_stride()) {
+    const int64_t base = r * D;
+    for (int64_t j = lane; j < D; j += 64) g[base + j] = -(q[base + j] * iv[j]);
+  }
+}
+
 // short rows (D <= 128, D % 4 == 0): G lanes per row, 64 / G rows per wave (see k_momentum_diag_short)
 template <int G>
 __global__ void __launch_bounds__(kBlock)
@@ -212,6 +273,34 @@ int bjx_target_diag_gaussian(void* stream, int64_t N, int64_t D, const float* in
     hipLaunchKernelGGL(k_diag_gaussian<1>, grid, block, 0, (hipStream_t)stream, N, D, inv_var, q,
                        logp_out, g_out);
   return bjx_check_launch("bjx_target_diag_gaussian");
+}
+
+int bjx_target_diag_gaussian_grad(void* stream, int64_t N, int64_t D, const float* inv_var, const float* q,
+                                  float* g_out) {
+  BJX_CHECK_ARG(N >= 0 && D > 0, "bjx_target_diag_gaussian_grad: bad arguments");
+  if (N == 0) return 0;  // an empty batch has no buffers to check
+  BJX_CHECK_ARG(inv_var && q && g_out, "bjx_target_diag_gaussian_grad: bad arguments");
+  const dim3 block(kBlock);
+  hipStream_t s = (hipStream_t)stream;
+  // the rule of the full kernel: a batch larger than the Infinity Cache streams from HBM
+  static const int nt_mode = [] { const char* e = getenv("BJX_LF_NT"); return e ? atoi(e) : -1; }();
+  const bool nt = nt_mode < 0 ? N * D * 8 > ((int64_t)256 << 20) : nt_mode != 0;
+  const bool v4 = bjx_vec4_ok(D, inv_var, q, g_out);
+  if (v4 && D % 1024 == 0 && N * (D / 1024) < ((int64_t)1 << 31)) {
+    const int bpr = (int)(D / 1024);
+    const dim3 grid((unsigned)(N * bpr));
+    if (nt) hipLaunchKernelGGL(k_diag_gaussian_grad_flat<true>, grid, block, 0, s, D, bpr, inv_var, q, g_out);
+    else hipLaunchKernelGGL(k_diag_gaussian_grad_flat<false>, grid, block, 0, s, D, bpr, inv_var, q, g_out);
+  } else if (v4 && N * (D / 4) < ((int64_t)1 << 31)) {
+    const uint32_t D4 = (uint32_t)(D / 4), total4 = (uint32_t)(N * (D / 4));
+    const dim3 grid((total4 + kBlock - 1) / kBlock);
+    if (nt) hipLaunchKernelGGL(k_diag_gaussian_grad_flat_any<true>, grid, block, 0, s, total4, D4, inv_var, q, g_out);
+    else hipLaunchKernelGGL(k_diag_gaussian_grad_flat_any<false>, grid, block, 0, s, total4, D4, inv_var, q, g_out);
+  } else {
+    hipLaunchKernelGGL(k_diag_gaussian_grad_rows, dim3(bjx_row_grid(N, kWavesPerBlock)), block, 0, s, N, D,
+                       inv_var, q, g_out);
+  }
+  return bjx_check_launch("bjx_target_diag_gaussian_grad");
 }
 
 int bjx_target_neal_funnel(void* stream, int64_t N, int64_t D, const float* q, float* logp_out,

@@ -219,4 +219,30 @@ __device__ __forceinline__ void target_rows(int64_t N, int64_t D, const float* p
   }
 }
 
+// The gradient alone (every evaluation of an HMC trajectory but its last, endpoint proposal): the same eval with
+// need_logp = false -- what hmc_trajectory_rows calls between two leapfrogs -- and no logp store.
+template <int NI, class Target>
+__device__ __forceinline__ void target_grad_rows(int64_t N, int64_t D, const float* params, const float* q,
+                                                 float* grad) {
+  const int lane = threadIdx.x & 63;
+  const int waves = blockDim.x >> 6;
+  for (int64_t r = (int64_t)blockIdx.x * waves + (threadIdx.x >> 6); r < N; r += (int64_t)gridDim.x * waves) {
+    typename Target::template Ctx<NI> ctx;
+    Target::template init<NI>(ctx, D, params);
+    F4 x[NI], g[NI];
+    float lp = 0.0f;
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+      const int64_t j = ((int64_t)lane + 64 * k) * 4;
+      if (j < D) x[k] = ld4(q + r * D + j);
+    }
+    Target::template eval<NI>(ctx, D, params, x, false, g, lp);
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+      const int64_t j = ((int64_t)lane + 64 * k) * 4;
+      if (j < D) st4(grad + r * D + j, g[k]);
+    }
+  }
+}
+
 }  // namespace bjx

@@ -443,6 +443,39 @@ extern "C" __global__ void __launch_bounds__(256) bjx_rtc_ew_rows(long long N, l
     if (lane == 0) logp[r] = lp;
   }}
 }}
+
+// the gradient alone: the same element-wise body without the row sums (a trajectory's intermediate evaluations)
+extern "C" __global__ void __launch_bounds__(256) bjx_rtc_ew_grad_rows(long long N, long long D, const float* __restrict__ params,
+                                                                        const float* __restrict__ q, float* __restrict__ grad) {{
+  const int lane = threadIdx.x & 63;
+  const int waves = blockDim.x >> 6;
+  for (int64_t r = (int64_t)blockIdx.x * waves + (threadIdx.x >> 6); r < N; r += (int64_t)gridDim.x * waves) {{
+    const float* qr = q + r * D;
+    float* gr = grad + r * D;
+    if (D % 4 == 0) {{
+      F4 xq[4]; {p_decl_arr}
+      row_sweep4<4>(lane, D,
+        [&](int u, int64_t j) {{ xq[u] = ld4(qr + j); {p_load_u}}},
+        [&](int u, int64_t j) {{
+          const float xs[4] = {{xq[u].x, xq[u].y, xq[u].z, xq[u].w}}; {p_unpack_u}
+          float gs[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {{
+            const float x = xs[e]; {p_decl}
+            {body}
+            gs[e] = {g_expr};
+          }}
+          st4(gr + j, F4{{gs[0], gs[1], gs[2], gs[3]}});
+        }});
+    }} else {{
+      for (int64_t j = lane; j < D; j += 64) {{
+        const float x = qr[j]; {p_scalar}
+        {body}
+        gr[j] = {g_expr};
+      }}
+    }}
+  }}
+}}
 """
     params = torch.stack(gen.params).contiguous() if gen.params else None
     src = ElementwiseSource(source, params, len(used),

@@ -17,8 +17,8 @@ from typing import Callable, NamedTuple
 import torch
 
 from . import _lib, integrators, metrics
-from ._util import (new_graph, record_graph, check_batch, eval_logdensity, is_capturable, step_size_args, value_and_grad,
-                    warn_eager_driver)
+from ._util import (new_graph, record_graph, check_batch, eval_into, eval_logdensity, is_capturable, step_size_args,
+                    value_and_grad, warn_eager_driver)
 from .base import SamplingAlgorithm
 from .random import key_spec
 
@@ -263,6 +263,10 @@ class _GraphedTrajectory:
         self.eps = torch.ones(n, dtype=torch.float32, device=device)
         self.imm = torch.ones((n, D) if imm_per_chain else (D,), dtype=torch.float32, device=device)
         self.imm_stride = D if imm_per_chain else 0
+        # the callable's outputs: written in place by callables that can (``_util.eval_into``), so the recording
+        # works on q, p and ONE gradient array
+        self._g = torch.empty((n, D), dtype=torch.float32, device=device)
+        self._logp = torch.empty(n, dtype=torch.float32, device=device)
         self.Wq.zero_()
         self.Wp.zero_()
         self._vg = vg
@@ -279,15 +283,16 @@ class _GraphedTrajectory:
 
     def _body(self):
         stream = _lib.current_stream()
-        logp, g = eval_logdensity(self._vg, self.Wq)
-        for _ in range(self.L - 1):
+        # only the last evaluation's logp is read (endpoint proposal): the others are gradient-only where offered
+        logp, g = eval_into(self._vg, self.Wq, self._logp, self._g, need_logp=self.L == 1)
+        for i in range(self.L - 1):
             _lib.call("bjx_leapfrog_diag", stream, self.n, self.D, 2, 0.0, self.eps.data_ptr(),
                       self.imm.data_ptr(), self.imm_stride, self.Wq.data_ptr(), self.Wp.data_ptr(),
                       g.data_ptr(), self.Wq.data_ptr(), self.Wp.data_ptr())
-            # release the consumed gradient first so the (stream-ordered) allocator hands the same
-            # block to the callable again: the block's working set stays q, p, g (3 arrays)
+            # a callable that allocates its own outputs: release the consumed gradient first so the
+            # (stream-ordered) allocator hands the same block to it again (working set q, p, g: 3 arrays)
             del logp, g
-            logp, g = eval_logdensity(self._vg, self.Wq)
+            logp, g = eval_into(self._vg, self.Wq, self._logp, self._g, need_logp=i == self.L - 2)
         return logp, g
 
 
@@ -422,8 +427,11 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: f
         # unless the whole batch is one un-graphed block, in which case they ARE the result
         q_end = torch.empty_like(q0) if L > 0 else q0
         p_work = torch.empty_like(q0) if (L > 0 and not graphed) else None
-        g_end = torch.empty_like(q0) if (L > 0 and not single) else None
-        logp_end = torch.empty_like(logp0) if (L > 0 and not single) else None
+        # (a callable that evaluates into the caller's buffers writes g / logp of every block straight here, one
+        # un-graphed block included; the outputs of any other callable are copied in, or adopted when single)
+        writes_into = getattr(vg, "_bjx_eval_into", None) is not None
+        g_end = torch.empty_like(q0) if (L > 0 and (not single or writes_into)) else None
+        logp_end = torch.empty_like(logp0) if (L > 0 and (not single or writes_into)) else None
         if L == 0:
             g_end, logp_end = g0, logp0
 
@@ -452,6 +460,18 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: f
             nonlocal g_end, logp_end
             stream = _lib.current_stream()
             n, sl, m, eb, boff = block_args(b)
+            # the block's ONE gradient buffer (and logp): its slice of the result arrays
+            if L > 0 and g_end is not None:
+                g_buf, logp_buf = (g_end, logp_end) if single else (g_end[sl], logp_end[sl])
+            else:
+                g_buf = logp_buf = None
+
+            def evaluate(q_, need_logp):
+                """One log-density evaluation of the trajectory; ``need_logp`` is true for the last one only."""
+                if g_buf is None:
+                    return eval_logdensity(vg, q_)
+                return eval_into(vg, q_, logp_buf, g_buf, need_logp)
+
             if fused_first:
                 q, p = q_end[sl], p_work[sl]
                 launch_first(b, stream)
@@ -499,7 +519,8 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: f
                                                g_in, q, p_out)
 
                 first = True
-                for _ in range(L):
+                logp = g = None
+                for i in range(L):
                     for si, a_c in enumerate(drift_c):
                         if first:
                             p = stage(1, kick_c[0], 0.0, a_c, q0[sl], p0[sl], g0[sl], p)
@@ -508,7 +529,8 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: f
                             p = stage(2, kick_c[-1], kick_c[0], a_c, q, p, g, p)
                         else:
                             p = stage(1, kick_c[si], 0.0, a_c, q, p, g, p)
-                        logp, g = eval_logdensity(vg, q)
+                        del logp, g  # consumed: a callable that allocates its outputs gets the same block again
+                        logp, g = evaluate(q, i == L - 1 and si == len(drift_c) - 1)
                         yield
                         stream = _lib.current_stream()
                 eps_fin, eps_pc_fin = eps, eb
@@ -516,12 +538,15 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: f
                 if not fused_first:
                     q, p = q_end[sl], p_work[sl]
                     p = _launch_leapfrog(stream, m, n, D, 1, eps, eb, q0[sl], p0[sl], g0[sl], q, p)
-                logp, g = eval_logdensity(vg, q)
-                for _ in range(L - 1):
+                logp, g = evaluate(q, L == 1)
+                for i in range(L - 1):
                     yield
                     stream = _lib.current_stream()
                     p = _launch_leapfrog(stream, m, n, D, 2, eps, eb, q, p, g, q, p)
-                    logp, g = eval_logdensity(vg, q)
+                    # consumed: a callable that allocates its own outputs gets the same block back from the
+                    # (stream-ordered) allocator, so the block's working set stays q, p, g (3 arrays)
+                    del logp, g
+                    logp, g = evaluate(q, i == L - 2)
                 yield
                 stream = _lib.current_stream()
                 eps_fin, eps_pc_fin = eps, eb
@@ -556,13 +581,15 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: f
                              logp_new[sl], g_new[sl], acc_rate[sl], is_acc[sl], is_div[sl],
                              energy[sl])
             if L > 0:
-                if single:
+                if g is g_buf:  # (and logp is logp_buf: the last evaluation is never gradient-only)
+                    pass        # the callable wrote the block's end state where it belongs
+                elif single:
                     g_end, logp_end = g, logp
                 else:
                     g_end[sl].copy_(g)
                     logp_end[sl].copy_(logp)
-                    if graphed:
-                        q_end[sl].copy_(q)
+                if graphed:
+                    q_end[sl].copy_(q)
 
 
         # Blocks are independent, so up to `n_streams` of them are advanced in turn, each on its own

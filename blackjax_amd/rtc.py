@@ -140,6 +140,11 @@ using namespace bjx;
                                                                        const float* params, const float* q, \\
                                                                        float* logp, float* grad) {        \\
     target_rows<NI_, %(struct)s>(N, D, params, q, logp, grad);                                            \\
+  }                                                                                                       \\
+  extern "C" __global__ void __launch_bounds__(256) bjx_rtc_grad_##NI_(long long N, long long D,          \\
+                                                                       const float* params, const float* q, \\
+                                                                       float* grad) {                     \\
+    target_grad_rows<NI_, %(struct)s>(N, D, params, q, grad);                                             \\
   }
 BJX_RTC_KERNELS(1)
 BJX_RTC_KERNELS(2)

@@ -27,6 +27,15 @@ class _Target:
         q = check_batch(q, "q")
         return q, torch.empty(q.shape[0], dtype=torch.float32, device=q.device), torch.empty_like(q)
 
+    # Optional capabilities of a value-and-grad callable (``_util.eval_into``), which the HMC driver uses when present:
+    #   _bjx_eval_into(q, logp_out, g_out)  evaluate INTO the caller's contiguous fp32 buffers (n,), (n, D);
+    #   _bjx_grad_into(q, g_out)            the gradient alone, bit for bit the g of the full evaluation.
+    # Either may return False ("not this time": nothing was written, call me the ordinary way).
+    def __call__(self, q):
+        q, logp, g = self._alloc(q)
+        self._bjx_eval_into(q, logp, g)
+        return logp, g
+
 
 class DiagGaussian(_Target):
     def __init__(self, inv_var: torch.Tensor):
@@ -40,26 +49,29 @@ class DiagGaussian(_Target):
             return 2, self.inv_var
         return None
 
-    def __call__(self, q):
-        q, logp, g = self._alloc(q)
+    def _bjx_eval_into(self, q, logp, g):
         N, D = q.shape
         if self.inv_var.shape != (D,):
             raise ValueError(f"inv_var has shape {tuple(self.inv_var.shape)}, expected ({D},)")
         _lib.call("bjx_target_diag_gaussian", _lib.current_stream(), N, D, self.inv_var.data_ptr(),
                   q.data_ptr(), logp.data_ptr(), g.data_ptr())
-        return logp, g
+
+    def _bjx_grad_into(self, q, g):
+        N, D = q.shape
+        if self.inv_var.shape != (D,):
+            raise ValueError(f"inv_var has shape {tuple(self.inv_var.shape)}, expected ({D},)")
+        _lib.call("bjx_target_diag_gaussian_grad", _lib.current_stream(), N, D, self.inv_var.data_ptr(),
+                  q.data_ptr(), g.data_ptr())
 
 
 class NealFunnel(_Target):
     def _bjx_fused_target(self, dim: int):
         return 1, None
 
-    def __call__(self, q):
-        q, logp, g = self._alloc(q)
+    def _bjx_eval_into(self, q, logp, g):
         N, D = q.shape
         _lib.call("bjx_target_neal_funnel", _lib.current_stream(), N, D, q.data_ptr(),
                   logp.data_ptr(), g.data_ptr())
-        return logp, g
 
 
 class AR1Gaussian(_Target):
@@ -74,14 +86,12 @@ class AR1Gaussian(_Target):
         i = torch.arange(self.dim, device=device)
         return (self.rho ** (i[:, None] - i[None, :]).abs().double()).float()
 
-    def __call__(self, q):
-        q, logp, g = self._alloc(q)
+    def _bjx_eval_into(self, q, logp, g):
         N, D = q.shape
         if D != self.dim:
             raise ValueError(f"expected dim {self.dim}, got {D}")
         _lib.call("bjx_target_ar1_gaussian", _lib.current_stream(), N, D, self.d_edge, self.d_mid,
                   self.off, q.data_ptr(), logp.data_ptr(), g.data_ptr())
-        return logp, g
 
 
 class DeviceTarget(_Target):
@@ -154,23 +164,26 @@ class DeviceTarget(_Target):
     def _bjx_fused_target(self, dim: int):
         return ("rtc", self) if dim % 4 == 0 and dim <= 1024 else None
 
-    def __call__(self, q):
+    def _launch_rows(self, kernel, q, *outs):
         import ctypes
 
         from . import rtc
 
-        q, logp, g = self._alloc(q)
         N, D = q.shape
         if D % 4 != 0 or D > 1024:
             raise ValueError("DeviceTarget: rows of at most 1 024 floats, a multiple of 4")
         if N == 0:
-            return logp, g
+            return
         grid = min((N + 3) // 4, 1 << 20)
-        self.module().launch(f"bjx_rtc_eval_{rtc.ni_for(D)}", grid, 256, _lib.current_stream(),
+        self.module().launch(f"{kernel}_{rtc.ni_for(D)}", grid, 256, _lib.current_stream(),
                              ctypes.c_longlong(N), ctypes.c_longlong(D), ctypes.c_void_p(self._params_ptr(q.device)),
-                             ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(logp.data_ptr()),
-                             ctypes.c_void_p(g.data_ptr()))
-        return logp, g
+                             ctypes.c_void_p(q.data_ptr()), *[ctypes.c_void_p(t.data_ptr()) for t in outs])
+
+    def _bjx_eval_into(self, q, logp, g):
+        self._launch_rows("bjx_rtc_eval", q, logp, g)
+
+    def _bjx_grad_into(self, q, g):
+        self._launch_rows("bjx_rtc_grad", q, g)
 
 
 class ElementwiseRowsTarget(_Target):
@@ -199,22 +212,26 @@ class ElementwiseRowsTarget(_Target):
     def _bjx_fused_target(self, dim: int):
         return None
 
-    def __call__(self, q):
+    def _launch_rows(self, kernel, q, *outs):
         import ctypes
 
-        q, logp, g = self._alloc(q)
         N, D = q.shape
         if D != self.dim:
             raise ValueError(f"this target was generated for D = {self.dim}, got {D}")
         if N == 0:
-            return logp, g
+            return
         if self.params is not None and self.params.device != q.device:
             raise ValueError(f"params live on {self.params.device}, the chains on {q.device}")
         grid = min((N + 3) // 4, 1 << 20)
-        self.module().launch("bjx_rtc_ew_rows", grid, 256, _lib.current_stream(), ctypes.c_longlong(N),
+        self.module().launch(kernel, grid, 256, _lib.current_stream(), ctypes.c_longlong(N),
                              ctypes.c_longlong(D), ctypes.c_void_p(0 if self.params is None else self.params.data_ptr()),
-                             ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(logp.data_ptr()), ctypes.c_void_p(g.data_ptr()))
-        return logp, g
+                             ctypes.c_void_p(q.data_ptr()), *[ctypes.c_void_p(t.data_ptr()) for t in outs])
+
+    def _bjx_eval_into(self, q, logp, g):
+        self._launch_rows("bjx_rtc_ew_rows", q, logp, g)
+
+    def _bjx_grad_into(self, q, g):
+        self._launch_rows("bjx_rtc_ew_grad_rows", q, g)
 
 
 def from_elementwise(fn, dim: int, device="cuda"):

@@ -465,6 +465,11 @@ int bjx_welford_final_diag(void* stream, int64_t N, int64_t D, int64_t sample_si
  *   ar1 gaussian:   Sigma_ij = rho^|i-j| (tridiagonal precision)                         */
 int bjx_target_diag_gaussian(void* stream, int64_t N, int64_t D, const float* inv_var,
                              const float* q, float* logp_out, float* g_out);
+/* The gradient alone, g = -(q*inv_var), bit for bit the g_out of bjx_target_diag_gaussian: what an HMC trajectory
+ * with the endpoint proposal needs from every evaluation but its last.  No row reduction, so the launch is one
+ * 16-byte piece per lane (D % 4 == 0 and 16-byte aligned buffers; a scalar row loop otherwise). */
+int bjx_target_diag_gaussian_grad(void* stream, int64_t N, int64_t D, const float* inv_var,
+                                  const float* q, float* g_out);
 int bjx_target_neal_funnel(void* stream, int64_t N, int64_t D, const float* q,
                            float* logp_out, float* g_out);
 int bjx_target_ar1_gaussian(void* stream, int64_t N, int64_t D, float diag_edge,

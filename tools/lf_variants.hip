@@ -86,6 +86,49 @@ __global__ void __launch_bounds__(256) grad_flat(const F4* __restrict__ q, F4* _
   }
 }
 
+// ---- the callable of the headline bench (DiagGaussian: g = -(q*inv_var), logp = 0.5 sum q*g) in its two forms,
+// run in the product's order: leapfrog (one piece per lane, last row first) ; callable (first row first)
+__global__ void __launch_bounds__(256) lf_piece_rev(F4* q, F4* p, const F4* __restrict__ g, const F4* __restrict__ imm,
+                                                    float h, float ed) {
+  const size_t i = (size_t)(gridDim.x - 1 - blockIdx.x) * 256 + threadIdx.x;
+  F4 pp = p[i], gg = g[i], qq = q[i];
+  const F4 mm = imm[threadIdx.x];
+  lf_math(pp, gg, qq, mm, h, ed);
+  p[i] = pp; q[i] = qq;
+}
+// row + reduction (k_diag_gaussian<4>): one wave per row, fp64 sum of q*g, wave reduction, logp store
+__global__ void __launch_bounds__(256) call_row_logp(const F4* __restrict__ q, F4* __restrict__ g, const F4* __restrict__ iv,
+                                                     float* __restrict__ logp, size_t N) {
+  const int lane = threadIdx.x & 63;
+  for (size_t r = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < N; r += (size_t)gridDim.x * 4) {
+    const size_t base = r * D4;
+    F4 a[4], v[4];
+    double acc = 0.0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) { a[u] = q[base + lane + 64 * u]; v[u] = iv[lane + 64 * u]; }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const F4 o{-(a[u].x * v[u].x), -(a[u].y * v[u].y), -(a[u].z * v[u].z), -(a[u].w * v[u].w)};
+      acc += (double)a[u].x * (double)o.x; acc += (double)a[u].y * (double)o.y;
+      acc += (double)a[u].z * (double)o.z; acc += (double)a[u].w * (double)o.w;
+      g[base + lane + 64 * u] = o;
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) logp[r] = (float)(0.5 * acc);
+  }
+}
+// flat gradient-only (k_diag_gaussian_grad_flat<.>): one piece per lane, one workgroup per 4 KB span, ascending;
+// XCD = true is the product's numbering (grad_span_of_workgroup)
+// XCD: workgroup b runs on XCD b % 8 and lf_piece_rev gives span s to workgroup grid - 1 - s, i.e. (grid % 8 == 0) to
+// XCD 7 - s % 8; with b ^ 7 the callable reads and writes span s on that same XCD (its 4 MiB L2 is not shared)
+template <bool XCD>
+__global__ void __launch_bounds__(256) call_piece_grad(const F4* __restrict__ q, F4* __restrict__ g,
+                                                       const F4* __restrict__ iv) {
+  const size_t i = (size_t)(XCD ? blockIdx.x ^ 7u : blockIdx.x) * 256 + threadIdx.x;
+  const F4 a = q[i], v = iv[threadIdx.x];
+  g[i] = F4{-(a.x * v.x), -(a.y * v.y), -(a.z * v.z), -(a.w * v.w)};
+}
+
 // pseudo-random fill: all-zero buffers toggle no data lines and flatter a power-limited part
 __global__ void fill_random(float* a, size_t n, unsigned seed, float lo, float hi) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -160,6 +203,40 @@ int main(int argc, char** argv) {
       printf("N %6zu v%d : loop %7.1f us/step (%5.2f TB/s of 28 B) | lf alone %6.1f us (%5.2f TB/s) | grad alone %6.1f us (%5.2f TB/s)\n",
              N, v, best_loop * 1e3 / L, (bytes_lf + bytes_gr) / (best_loop * 1e-3 / L) / 1e12, best_lf * 1e3 / L,
              bytes_lf / (best_lf * 1e-3 / L) / 1e12, best_gr * 1e3 / L, bytes_gr / (best_gr * 1e-3 / L) / 1e12);
+    }
+  }
+  // the callable's two forms between product-shaped leapfrogs (what one HMC trajectory launches)
+  float* logp; hipMalloc(&logp, maxN * 4);
+  for (size_t N : {(size_t)16384, (size_t)65536}) {
+    const unsigned pieces = (unsigned)(N * D4 / 256), rowgrid = (unsigned)(N / 4 < 65536 ? N / 4 : 65536);
+    for (int v = 0; v < 3; ++v) {
+      auto lf = [&]() { lf_piece_rev<<<pieces, 256>>>(q, p, g, imm, h, ed); };
+      auto cl = [&]() {
+        if (v == 0) call_row_logp<<<rowgrid, 256>>>(q, g, pr, logp, N);
+        else if (v == 1) call_piece_grad<false><<<pieces, 256>>>(q, g, pr);
+        else call_piece_grad<true><<<pieces, 256>>>(q, g, pr);
+      };
+      float best_loop = 1e30f, best_cl = 1e30f;
+      for (int rep = 0; rep < 6; ++rep) {
+        // q drifts under 50 leapfrogs: start every repetition from the same bounded pseudo-random state
+        if (randomize) {
+          fill_random<<<4096, 256>>>((float*)q, N * 1024, 1u, -1.0f, 1.0f);
+          fill_random<<<4096, 256>>>((float*)p, N * 1024, 2u, -1.0f, 1.0f);
+        }
+        hipEventRecord(e0);
+        for (int s = 0; s < L; ++s) { lf(); cl(); }
+        hipEventRecord(e1);
+        for (int s = 0; s < L; ++s) cl();
+        hipEventRecord(e2);
+        hipEventSynchronize(e2);
+        float a, b; hipEventElapsedTime(&a, e0, e1); hipEventElapsedTime(&b, e1, e2);
+        if (rep && a < best_loop) best_loop = a;
+        if (rep && b < best_cl) best_cl = b;
+      }
+      const double bytes_cl = 8.0 * N * 1024;
+      printf("N %6zu callable %-25s : lf+callable %7.1f us/step | callable alone %6.1f us (%5.2f TB/s of 8 B)\n", N,
+             v == 0 ? "row+logp (full)" : v == 1 ? "piece-per-lane (grad)" : "piece-per-lane, same XCD", best_loop * 1e3 / L, best_cl * 1e3 / L,
+             bytes_cl / (best_cl * 1e-3 / L) / 1e12);
     }
   }
   return 0;
