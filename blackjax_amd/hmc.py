@@ -12,13 +12,14 @@ only sequences launches around the user's PyTorch log-density callable.
 """
 from __future__ import annotations
 
-from typing import Callable, NamedTuple
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
 from . import _lib, integrators, metrics
 from ._util import (new_graph, record_graph, check_batch, eval_into, eval_logdensity, is_capturable, step_size_args,
                     value_and_grad, warn_eager_driver)
+from ._traj_launch import Launcher
 from .base import SamplingAlgorithm
 from .random import key_spec
 
@@ -70,20 +71,6 @@ def init(position: torch.Tensor, logdensity_fn: Callable) -> HMCState:
     return HMCState(position, logp, grad)
 
 
-_FUSE_FIRST = __import__("os").environ.get("BJX_HMC_FUSE_FIRST", "1") != "0"  # A/B switch (NOTEBOOK.md section 5)
-
-
-def _launch_leapfrog(stream, metric, N, D, n_kicks, eps, eps_pc, q_in, p_in, g, q_out, p_out):
-    if metric.kind == "diag":
-        _lib.call("bjx_leapfrog_diag", stream, N, D, n_kicks, eps, _lib.ptr(eps_pc),
-                  metric.imm.data_ptr(), metric.imm_stride, q_in.data_ptr(), p_in.data_ptr(),
-                  g.data_ptr(), q_out.data_ptr(), p_out.data_ptr())
-        return p_out
-    from . import dense
-
-    return dense.leapfrog(stream, metric, N, D, n_kicks, eps, eps_pc, q_in, p_in, g, q_out, p_out)
-
-
 class _ProposalKind:
     def __init__(self, name):
         self.name = name
@@ -97,123 +84,76 @@ hmc_proposal = _ProposalKind("hmc_proposal")
 multinomial_hmc_proposal = _ProposalKind("multinomial_hmc_proposal")
 
 
-def _build_mhmc_kernel(thr: float, kick_c=(0.5, 0.5), drift_c=(1.0,)):
-    """blackjax.mhmc: ``build_kernel(build_proposal=multinomial_hmc_proposal)`` (hmc.py:181-248 with
+def _prologue(rng_key, state, logdensity_fn, step_size, inverse_mass_matrix, chain_offset):
+    """The validated inputs of one transition: ``q0, logp0, g0, N, D, key, vg, metric, eps, eps_pc, stream, off``
+    (``key`` = ``key_spec``'s (k0, k1, fold); ``eps, eps_pc`` = ``step_size_args``')."""
+    q0 = check_batch(state.position, "state.position")
+    logp0 = check_batch(state.logdensity, "state.logdensity")
+    g0 = check_batch(state.logdensity_grad, "state.logdensity_grad")
+    N, D = q0.shape
+    metric = metrics.default_metric(inverse_mass_matrix, N, D, q0.device)
+    eps, eps_pc = step_size_args(step_size, N, q0.device)
+    return (q0, logp0, g0, N, D, key_spec(rng_key), value_and_grad(logdensity_fn), metric, eps, eps_pc,
+            _lib.current_stream(), int(chain_offset))
+
+
+def _multinomial_transition(thr, kick_c, drift_c, rng_key, state, logdensity_fn, step_size, inverse_mass_matrix, L,
+                            chain_offset=0, draw_steps=None):
+    """blackjax.mhmc / dmhmc: ``build_kernel(build_proposal=multinomial_hmc_proposal)`` (hmc.py:181-248 with
     trajectory.static_progressive_integration 170-232).  Instead of the trajectory end point, one
     state of the whole trajectory is drawn proportionally to exp(-H) by progressive (reservoir)
-    sampling; there is no Metropolis rejection (``is_accepted`` is always True)."""
+    sampling; there is no Metropolis rejection (``is_accepted`` is always True).  ``draw_steps(device)`` (dmhmc; called
+    once the inputs are validated) returns per-chain trajectory lengths ``(n_steps, shortest, longest)``: ``L`` is then
+    the longest, every launch after the opening one is masked by them, and finished chains keep their q, so the
+    callable returns the same (logp, g) for them again, unused.
 
+    Any palindromic integrator [b1, a1, ..., b1] (integrators.py:104-150): a step is closed with (eps b1) g and the
+    next one opened with (eps b1) g, (eps a1) M^{-1} p (``Launcher.mhmc_step``: one launch with a diagonal metric; with
+    a dense one the next leapfrog starts from the fully kicked momentum with its own, separately rounded, opening
+    kick); the stages in between are plain kick + drift launches, each followed by the callable."""
+    q0, logp0, g0, N, D, key, vg, metric, eps, eps_pc, stream, off = _prologue(
+        rng_key, state, logdensity_fn, step_size, inverse_mass_matrix, chain_offset)
+    dev = q0.device
+    n_steps = None
+    if draw_steps is not None:
+        n_steps, _, L = draw_steps(dev)
+    general = tuple(kick_c) != (0.5, 0.5) or tuple(drift_c) != (1.0,)
+    lau = Launcher(metric, kick_c, drift_c, general, "mhmc" if n_steps is None else "dmhmc")
+    p0 = torch.empty_like(q0)
+    ke0 = torch.empty_like(logp0)
+    lau.momentum(stream, key, off, N, D, p0, ke0)
+    weight = torch.zeros_like(logp0)
+    slpa = torch.full_like(logp0, float("-inf"))
+    any_div = torch.zeros(N, dtype=torch.bool, device=dev)
+    ever = torch.zeros(N, dtype=torch.bool, device=dev)
+    pq, pp, pg = torch.empty_like(q0), torch.empty_like(q0), torch.empty_like(q0)
+    plogp, penergy, acc_rate = torch.empty_like(logp0), torch.empty_like(logp0), torch.empty_like(logp0)
+    if L > 0:
+        q = torch.empty_like(q0)
+        p = lau.stage(stream, N, D, 1, lau.kick_c[0], 0.0, lau.drift_c[0], eps, eps_pc, q0, p0, g0, q,
+                      torch.empty_like(q0))
+    for i in range(L):
+        logp, g = eval_logdensity(vg, q)
+        for si in range(1, len(lau.drift_c)):  # stages 2 .. K
+            p = lau.stage(stream, N, D, 1, lau.kick_c[si], 0.0, lau.drift_c[si], eps, eps_pc, q, p, g, q, None,
+                          n_steps, 0 if n_steps is None else i)
+            logp, g = eval_logdensity(vg, q)
+        p = lau.mhmc_step(stream, key, off, N, D, i, i + 1 < L, eps, eps_pc, thr, logp0, ke0, q, p, g, logp, weight,
+                          slpa, any_div, ever, pq, pp, pg, plogp, penergy, n_steps=n_steps)
+    lau.mhmc_finish(stream, N, D, L, n_steps, q0, p0, g0, logp0, ke0, ever, slpa, pq, pp, pg, plogp, penergy, acc_rate)
+    info = HMCInfo(p0, acc_rate, torch.ones(N, dtype=torch.bool, device=dev), any_div, penergy,
+                   IntegratorState(pq, pp, plogp, pg), L if n_steps is None else n_steps)
+    return HMCState(pq, plogp, pg), info
+
+
+def _build_mhmc_kernel(thr: float, kick_c=(0.5, 0.5), drift_c=(1.0,)):
     def kernel(rng_key, state: HMCState, logdensity_fn: Callable, step_size,
                inverse_mass_matrix, num_integration_steps: int, *, chain_offset: int = 0):
-        q0 = check_batch(state.position, "state.position")
-        logp0 = check_batch(state.logdensity, "state.logdensity")
-        g0 = check_batch(state.logdensity_grad, "state.logdensity_grad")
-        N, D = q0.shape
         L = int(num_integration_steps)
         if L < 0:
             raise ValueError("num_integration_steps must be >= 0")
-        k0, k1, fold = key_spec(rng_key)
-        vg = value_and_grad(logdensity_fn)
-        metric = metrics.default_metric(inverse_mass_matrix, N, D, q0.device)
-        eps, eps_pc = step_size_args(step_size, N, q0.device)
-        stream = _lib.current_stream()
-        off = int(chain_offset)
-        dev = q0.device
-        is_diag = metric.kind == "diag"
-        if is_diag:
-            imm_p, imm_s = metric.imm.data_ptr(), metric.imm_stride
-
-        p0 = torch.empty_like(q0)
-        ke0 = torch.empty_like(logp0)
-        if is_diag:
-            _lib.call("bjx_hmc_momentum_diag", stream, k0, k1, off, fold, N, D, imm_p, imm_s,
-                      p0.data_ptr(), ke0.data_ptr())
-        else:
-            from . import dense
-
-            dense.momentum(stream, metric, k0, k1, off, fold, N, D, p0, ke0)
-        weight = torch.zeros_like(logp0)
-        slpa = torch.full_like(logp0, float("-inf"))
-        any_div = torch.zeros(N, dtype=torch.bool, device=dev)
-        ever = torch.zeros(N, dtype=torch.bool, device=dev)
-        pq, pp, pg = torch.empty_like(q0), torch.empty_like(q0), torch.empty_like(q0)
-        plogp, penergy = torch.empty_like(logp0), torch.empty_like(logp0)
-        acc_rate = torch.empty_like(logp0)
-        general = tuple(kick_c) != (0.5, 0.5) or tuple(drift_c) != (1.0,)
-        if L > 0 and is_diag and general:
-            # any palindromic integrator [b1, a1, ..., b1] (integrators.py:104-150): the fused step kernel
-            # closes a step with (eps b1) g and opens the next with (eps b1) g, (eps a1) M^{-1} p; the
-            # stages in between are plain kick + drift launches, each followed by the callable
-            b1, a1 = float(kick_c[0]), float(drift_c[0])
-            q, p = torch.empty_like(q0), torch.empty_like(q0)
-            _lib.call("bjx_leapfrog_diag_coef", stream, N, D, 1, b1, 0.0, a1, eps, _lib.ptr(eps_pc), imm_p,
-                      imm_s, q0.data_ptr(), p0.data_ptr(), g0.data_ptr(), q.data_ptr(), p.data_ptr(), None, 0)
-            for i in range(L):
-                logp, g = eval_logdensity(vg, q)
-                for si in range(1, len(drift_c)):
-                    _lib.call("bjx_leapfrog_diag_coef", stream, N, D, 1, float(kick_c[si]), 0.0,
-                              float(drift_c[si]), eps, _lib.ptr(eps_pc), imm_p, imm_s, q.data_ptr(),
-                              p.data_ptr(), g.data_ptr(), q.data_ptr(), p.data_ptr(), None, 0)
-                    logp, g = eval_logdensity(vg, q)
-                _lib.call("bjx_mhmc_step_diag_coef", stream, k0, k1, off, fold, N, D, i,
-                          1 if i + 1 < L else 0, eps, _lib.ptr(eps_pc), imm_p, imm_s, thr,
-                          logp0.data_ptr(), ke0.data_ptr(), q.data_ptr(), p.data_ptr(), g.data_ptr(),
-                          logp.data_ptr(), weight.data_ptr(), slpa.data_ptr(), any_div.data_ptr(),
-                          ever.data_ptr(), pq.data_ptr(), pp.data_ptr(), pg.data_ptr(),
-                          plogp.data_ptr(), penergy.data_ptr(), None, b1, a1)
-        elif L > 0 and general:
-            # dense metric x any palindromic integrator (round 4): opening (b1, a1), the stages in between and the
-            # re-opening of the next step are bjx_leapfrog_dense_coef launches (kick prologue + GEMM / mat-vec +
-            # drift epilogue), the closing kick b1 + reservoir step is bjx_mhmc_step_dense_coef
-            from . import dense
-
-            b1, a1 = float(kick_c[0]), float(drift_c[0])
-            q, p_half = torch.empty_like(q0), torch.empty_like(q0)
-            p_half = dense.leapfrog_coef(stream, metric, N, D, 1, b1, 0.0, a1, eps, eps_pc, q0, p0, g0, q, p_half)
-            for i in range(L):
-                logp, g = eval_logdensity(vg, q)
-                for si in range(1, len(drift_c)):
-                    p_half = dense.leapfrog_coef(stream, metric, N, D, 1, float(kick_c[si]), 0.0, float(drift_c[si]),
-                                                 eps, eps_pc, q, p_half, g, q, torch.empty_like(q0))
-                    logp, g = eval_logdensity(vg, q)
-                p1 = dense.mhmc_step(stream, metric, k0, k1, off, fold, N, D, i, eps, eps_pc, thr, logp0,
-                                     ke0, q, p_half, g, logp, weight, slpa, any_div, ever, pq, pp, pg,
-                                     plogp, penergy, kick_coef=b1)
-                if i + 1 < L:
-                    p_half = dense.leapfrog_coef(stream, metric, N, D, 1, b1, 0.0, a1, eps, eps_pc, q, p1, g, q,
-                                                 torch.empty_like(q0))
-        elif L > 0 and is_diag:
-            q, p = torch.empty_like(q0), torch.empty_like(q0)
-            _lib.call("bjx_leapfrog_diag", stream, N, D, 1, eps, _lib.ptr(eps_pc), imm_p, imm_s,
-                      q0.data_ptr(), p0.data_ptr(), g0.data_ptr(), q.data_ptr(), p.data_ptr())
-            for i in range(L):
-                logp, g = eval_logdensity(vg, q)
-                _lib.call("bjx_mhmc_step_diag", stream, k0, k1, off, fold, N, D, i,
-                          1 if i + 1 < L else 0, eps, _lib.ptr(eps_pc), imm_p, imm_s, thr,
-                          logp0.data_ptr(), ke0.data_ptr(), q.data_ptr(), p.data_ptr(), g.data_ptr(),
-                          logp.data_ptr(), weight.data_ptr(), slpa.data_ptr(), any_div.data_ptr(),
-                          ever.data_ptr(), pq.data_ptr(), pp.data_ptr(), pg.data_ptr(),
-                          plogp.data_ptr(), penergy.data_ptr())
-        elif L > 0:
-            # dense metric (shared matrix: MFMA GEMMs; per-chain matrices: fp64 matrix-vector kernels):
-            # opening kick + drift, callable, then closing kick + reservoir step; the next leapfrog
-            # starts from the fully kicked momentum with its own (separately rounded) opening kick
-            q, p_half = torch.empty_like(q0), torch.empty_like(q0)
-            p_half = dense.leapfrog(stream, metric, N, D, 1, eps, eps_pc, q0, p0, g0, q, p_half)
-            for i in range(L):
-                logp, g = eval_logdensity(vg, q)
-                p1 = dense.mhmc_step(stream, metric, k0, k1, off, fold, N, D, i, eps, eps_pc, thr, logp0,
-                                     ke0, q, p_half, g, logp, weight, slpa, any_div, ever, pq, pp, pg,
-                                     plogp, penergy)
-                if i + 1 < L:
-                    p_half = dense.leapfrog(stream, metric, N, D, 1, eps, eps_pc, q, p1, g, q, p_half)
-        _lib.call("bjx_mhmc_finish", stream, N, D, L, q0.data_ptr(), p0.data_ptr(), g0.data_ptr(),
-                  logp0.data_ptr(), ke0.data_ptr(), ever.data_ptr(), slpa.data_ptr(), pq.data_ptr(),
-                  pp.data_ptr(), pg.data_ptr(), plogp.data_ptr(), penergy.data_ptr(),
-                  acc_rate.data_ptr())
-        info = HMCInfo(p0, acc_rate, torch.ones(N, dtype=torch.bool, device=dev), any_div, penergy,
-                       IntegratorState(pq, pp, plogp, pg), L)
-        return HMCState(pq, plogp, pg), info
+        return _multinomial_transition(thr, kick_c, drift_c, rng_key, state, logdensity_fn, step_size,
+                                       inverse_mass_matrix, L, chain_offset=chain_offset)
 
     return kernel
 
@@ -262,7 +202,7 @@ class _GraphedTrajectory:
         self.Wp = torch.empty((n, D), dtype=torch.float32, device=device)
         self.eps = torch.ones(n, dtype=torch.float32, device=device)
         self.imm = torch.ones((n, D) if imm_per_chain else (D,), dtype=torch.float32, device=device)
-        self.imm_stride = D if imm_per_chain else 0
+        self._lau = Launcher(metrics.Metric("diag", self.imm, D if imm_per_chain else 0, None))
         # the callable's outputs: written in place by callables that can (``_util.eval_into``), so the recording
         # works on q, p and ONE gradient array
         self._g = torch.empty((n, D), dtype=torch.float32, device=device)
@@ -286,14 +226,49 @@ class _GraphedTrajectory:
         # only the last evaluation's logp is read (endpoint proposal): the others are gradient-only where offered
         logp, g = eval_into(self._vg, self.Wq, self._logp, self._g, need_logp=self.L == 1)
         for i in range(self.L - 1):
-            _lib.call("bjx_leapfrog_diag", stream, self.n, self.D, 2, 0.0, self.eps.data_ptr(),
-                      self.imm.data_ptr(), self.imm_stride, self.Wq.data_ptr(), self.Wp.data_ptr(),
-                      g.data_ptr(), self.Wq.data_ptr(), self.Wp.data_ptr())
+            self._lau.stage(stream, self.n, self.D, 2, 0.5, 0.5, 1.0, 0.0, self.eps, self.Wq, self.Wp, g, self.Wq,
+                            self.Wp)
             # a callable that allocates its own outputs: release the consumed gradient first so the
             # (stream-ordered) allocator hands the same block to it again (working set q, p, g: 3 arrays)
             del logp, g
             logp, g = eval_into(self._vg, self.Wq, self._logp, self._g, need_logp=i == self.L - 2)
         return logp, g
+
+
+class _GraphCache:
+    """The recordings of one kernel (``build_kernel``), keyed on block shape, trajectory length and the USER's
+    callable (each recording holds it)."""
+
+    def __init__(self):
+        self.graphs: dict = {}
+        self.not_capturable: dict = {}  # id -> callable whose capture failed once (the reference keeps the id from
+        #                                 being reused by another object)
+        self.seen: dict = {}            # calls per key that did not ``force``
+
+    def get(self, n, D, L, vg, fn, imm_per_chain, dev, force):
+        """The recording for blocks of ``n`` chains.  ``force`` (``use_graph=True``, and every block of a transition
+        that is graphed): record now if there is none, errors propagate.  Otherwise (``use_graph="auto"``): record on
+        the SECOND call with a given shape and trajectory length (a one-off call -- or a caller that varies L from
+        step to step -- should not pay for a recording), keep at most 8 recordings per kernel, and remember a callable
+        that cannot be recorded (or is broken: the plain path re-raises); ``None`` while there is no recording."""
+        key = (n, D, L, id(fn), imm_per_chain, dev.index)
+        if key in self.graphs:
+            return self.graphs[key]
+        if not force:
+            if id(fn) in self.not_capturable:
+                return None
+            self.seen[key] = self.seen.get(key, 0) + 1
+            if self.seen[key] < 2 or len(self.graphs) >= 8:
+                return None
+        try:
+            self.graphs[key] = _GraphedTrajectory(n, D, L, vg, imm_per_chain, dev, owner=fn)
+        except RuntimeError:
+            if force:
+                raise
+            self.not_capturable[id(fn)] = fn
+            torch.cuda.synchronize(dev)
+            return None
+        return self.graphs[key]
 
 
 _SIDE_STREAMS: dict = {}
@@ -304,6 +279,201 @@ def _side_streams(dev, n):
     while len(pool) < n:
         pool.append(torch.cuda.Stream(device=dev))
     return pool[:n]
+
+
+class _Block(NamedTuple):
+    """One chain block of a transition: its rows of the batch arrays, its launcher (per-chain matrices sliced), step
+    sizes and chain offset, and its ONE gradient buffer (and logp): its slice of the result arrays, or None when the
+    callable's own outputs are adopted."""
+
+    n: int
+    sl: slice
+    lau: Launcher
+    eps_pc: Optional[torch.Tensor]
+    off: int
+    g_buf: Optional[torch.Tensor]
+    logp_buf: Optional[torch.Tensor]
+
+
+class _Transition:
+    """One HMC transition for all chains (hmc.py:279-312 + hmc_proposal.generate 153-176), chain block by chain block.
+    The constructor validates the inputs, allocates the result arrays and decides blocking, streams and graphing;
+    ``run`` advances the blocks and returns ``(HMCState, HMCInfo)``."""
+
+    def __init__(self, thr, general, kick_c, drift_c, chain_block, streams, use_graph, graphs, rng_key, state,
+                 logdensity_fn, step_size, inverse_mass_matrix, num_integration_steps, chain_offset):
+        (self.q0, self.logp0, self.g0, N, D, self.key, self.vg, metric, self.eps, self.eps_pc, _,
+         self.off) = _prologue(rng_key, state, logdensity_fn, step_size, inverse_mass_matrix, chain_offset)
+        q0, logp0 = self.q0, self.logp0
+        L = int(num_integration_steps)
+        if L < 0:
+            raise ValueError("num_integration_steps must be >= 0")
+        self.N, self.D, self.L, self.thr = N, D, L, thr
+        self.fn, self.graphs, self.dev = logdensity_fn, graphs, q0.device
+        self.lau = Launcher(metric, kick_c, drift_c, general)
+        graphable = metric.kind == "diag" and not general
+
+        self.p0 = torch.empty_like(q0)
+        self.ke0 = torch.empty_like(logp0)
+        self.p_end = torch.empty_like(q0)
+        self.q_new = torch.empty_like(q0)
+        self.g_new = torch.empty_like(q0)
+        self.logp_new = torch.empty_like(logp0)
+        self.acc_rate = torch.empty_like(logp0)
+        self.energy = torch.empty_like(logp0)
+        self.is_acc = torch.empty(N, dtype=torch.bool, device=self.dev)
+        self.is_div = torch.empty(N, dtype=torch.bool, device=self.dev)
+
+        cb = chain_block
+        self.n_streams = 1 if streams == "auto" else streams
+        if cb == "auto":  # Infinity-Cache tiling pays for the streaming (diagonal) kernels only
+            if metric.kind == "diag":
+                cb = auto_chain_block(N, D, 3 + (1 if metric.imm_stride else 0))
+            elif metric.kind == "dense" and int(self.n_streams) > 1:
+                cb = -(-N // int(self.n_streams) // 128) * 128  # equal blocks of whole 128-row GEMM tiles
+            else:
+                cb = N
+        self.blk = blk = N if not cb or cb >= N else int(cb)
+        self.n_blocks = (N + blk - 1) // blk if N else 0
+        self.graphed = use_graph is True and L >= 1 and graphable
+        if use_graph == "auto" and L >= 2 and N > 0 and graphable and blk * D <= (1 << 21):
+            if is_capturable(logdensity_fn):
+                self.graphed = graphs.get(min(blk, N), D, L, self.vg, logdensity_fn, metric.imm_stride != 0,
+                                          self.dev, force=False) is not None
+            else:
+                warn_eager_driver(logdensity_fn, "hmc")  # small launches from Python: say so once
+        self.single = single = self.n_blocks <= 1 and not self.graphed
+        # end-of-trajectory state (HMCInfo.proposal): per-block work buffers are copied out
+        # unless the whole batch is one un-graphed block, in which case they ARE the result
+        self.q_end = torch.empty_like(q0) if L > 0 else q0
+        self.p_work = torch.empty_like(q0) if (L > 0 and not self.graphed) else None
+        # (a callable that evaluates into the caller's buffers writes g / logp of every block straight here, one
+        # un-graphed block included; the outputs of any other callable are copied in, or adopted when single)
+        writes_into = getattr(self.vg, "_bjx_eval_into", None) is not None
+        self.g_end = torch.empty_like(q0) if (L > 0 and (not single or writes_into)) else None
+        self.logp_end = torch.empty_like(logp0) if (L > 0 and (not single or writes_into)) else None
+        if L == 0:
+            self.g_end, self.logp_end = self.g0, logp0
+        self.fused_first = L > 0 and not self.graphed and self.lau.fuses_first(D)
+
+    def _block(self, b):
+        s, e = b * self.blk, min(self.N, (b + 1) * self.blk)
+        sl = slice(s, e)
+        g_buf = logp_buf = None
+        if self.L > 0 and self.g_end is not None:
+            g_buf, logp_buf = (self.g_end, self.logp_end) if self.single else (self.g_end[sl], self.logp_end[sl])
+        return _Block(e - s, sl, self.lau.rows(sl), None if self.eps_pc is None else self.eps_pc[sl], self.off + s,
+                      g_buf, logp_buf)
+
+    def _evaluate(self, blk, q, need_logp):
+        """One log-density evaluation of the trajectory; ``need_logp`` is true for the last one only."""
+        if blk.g_buf is None:
+            return eval_logdensity(self.vg, q)
+        return eval_into(self.vg, q, blk.logp_buf, blk.g_buf, need_logp)
+
+    def _stepwise(self, blk):
+        """The trajectory as plain launches, one per position update (generalized_two_stage_integrator,
+        integrators.py:104-150: the closing kick b_K of a step merges with the opening kick b_1 of the next; velocity
+        Verlet is the one-stage case, its first update possibly done by the momentum launch).  A generator: yields
+        after every log-density evaluation so that several blocks can be advanced in turn on their own streams."""
+        stream = _lib.current_stream()
+        sl, stage, n, D, eps, eps_pc = blk.sl, blk.lau.stage, blk.n, self.D, self.eps, blk.eps_pc
+        last = (self.L - 1, len(blk.lau.drift_c) - 1)
+        q_in, p_in, g = self.q0[sl], self.p0[sl], self.g0[sl]
+        q, p = self.q_end[sl], self.p_work[sl]
+        logp = None
+        for i, si, n_kicks, ka, kb, a in blk.lau.updates(self.L):
+            if q_in is q or not self.fused_first:  # (the momentum launch has done the first update)
+                p = stage(stream, n, D, n_kicks, ka, kb, a, eps, eps_pc, q_in, p_in, g, q, p)
+            q_in, p_in = q, p
+            # consumed: a callable that allocates its own outputs gets the same block back from the
+            # (stream-ordered) allocator, so the block's working set stays q, p, g (3 arrays)
+            del logp, g
+            logp, g = self._evaluate(blk, q, (i, si) == last)
+            yield
+            stream = _lib.current_stream()
+        return q, p, logp, g
+
+    def _graphed(self, blk):
+        """The trajectory as one graph replay: the first kick + drift writes straight into the static workspace."""
+        sl, m = blk.sl, blk.lau.metric
+        ctx = self.graphs.get(blk.n, self.D, self.L, self.vg, self.fn, m.imm_stride != 0, self.dev, force=True)
+        if blk.eps_pc is None:
+            ctx.eps.fill_(self.eps)
+        else:
+            ctx.eps.copy_(blk.eps_pc)
+        ctx.imm.copy_(m.imm)
+        blk.lau.stage(_lib.current_stream(), blk.n, self.D, 1, 0.5, 0.0, 1.0, self.eps, blk.eps_pc, self.q0[sl],
+                      self.p0[sl], self.g0[sl], ctx.Wq, ctx.Wp)
+        ctx.graph.replay()
+        return ctx.Wq, ctx.Wp, ctx.logp, ctx.g
+
+    def _finish(self, blk, eps, eps_pc, q, p, logp, g):
+        """Closing kick + accept / reject of one block, and its end state into the result arrays."""
+        sl = blk.sl
+        blk.lau.finish(_lib.current_stream(), self.key, blk.off, blk.n, self.D, eps, eps_pc, self.thr, self.q0[sl],
+                       self.logp0[sl], self.g0[sl], self.ke0[sl], q, logp, g, p, self.p_end[sl], self.q_new[sl],
+                       self.logp_new[sl], self.g_new[sl], self.acc_rate[sl], self.is_acc[sl], self.is_div[sl],
+                       self.energy[sl])
+        if self.L > 0:
+            if g is blk.g_buf:  # (and logp is logp_buf: the last evaluation is never gradient-only)
+                pass            # the callable wrote the block's end state where it belongs
+            elif self.single:
+                self.g_end, self.logp_end = g, logp
+            else:
+                self.g_end[sl].copy_(g)
+                self.logp_end[sl].copy_(logp)
+            if self.graphed:
+                self.q_end[sl].copy_(q)
+
+    def run_block(self, b):
+        """One chain block's transition as a generator (see ``_stepwise``)."""
+        blk = self._block(b)
+        sl = blk.sl
+        stream = _lib.current_stream()
+        if self.fused_first:
+            blk.lau.momentum_kick(stream, self.key, blk.off, blk.n, self.D, self.eps, blk.eps_pc, self.q0[sl],
+                                  self.g0[sl], self.p0[sl], self.ke0[sl], self.q_end[sl], self.p_work[sl])
+        else:
+            blk.lau.momentum(stream, self.key, blk.off, blk.n, self.D, self.p0[sl], self.ke0[sl])
+        if self.L == 0:
+            self._finish(blk, 0.0, None, self.q0[sl], self.p0[sl], self.logp0[sl], self.g0[sl])
+        elif self.graphed:
+            self._finish(blk, self.eps, blk.eps_pc, *self._graphed(blk))
+        else:
+            self._finish(blk, self.eps, blk.eps_pc, *(yield from self._stepwise(blk)))
+
+    def run(self):
+        """Blocks are independent, so up to ``streams`` of them are advanced in turn, each on its own HIP stream: one
+        block's callable (bandwidth-bound), the start-up of its launches and the output drain of a dense-metric GEMM
+        then overlap another block's kernels."""
+        n_blocks = self.n_blocks
+        ns = 1 if (self.graphed or n_blocks <= 1) else min(int(self.n_streams), n_blocks)
+        if ns <= 1:
+            for b in range(n_blocks):
+                for _ in self.run_block(b):
+                    pass
+        else:
+            main = torch.cuda.current_stream(self.dev)
+            pool = _side_streams(self.dev, ns)
+            for st_ in pool:
+                st_.wait_stream(main)
+            for w0 in range(0, n_blocks, ns):
+                active = [(self.run_block(b), pool[b - w0]) for b in range(w0, min(w0 + ns, n_blocks))]
+                while active:
+                    for item in list(active):
+                        with torch.cuda.stream(item[1]):
+                            try:
+                                next(item[0])
+                            except StopIteration:
+                                active.remove(item)
+            for st_ in pool:
+                main.wait_stream(st_)
+        if n_blocks == 0 and self.L > 0:
+            self.g_end, self.logp_end = self.g0, self.logp0
+        info = HMCInfo(self.p0, self.acc_rate, self.is_acc, self.is_div, self.energy,
+                       IntegratorState(self.q_end, self.p_end, self.logp_end, self.g_end), self.L)
+        return HMCState(self.q_new, self.logp_new, self.g_new), info
 
 
 def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: float = 1000,
@@ -340,288 +510,25 @@ def build_kernel(integrator=integrators.velocity_verlet, divergence_threshold: f
     if use_graph not in (True, False, "auto"):
         raise ValueError("use_graph must be True, False or 'auto'")
     thr = float(divergence_threshold)
+    # any palindromic coefficient list [b1, a1, ..., b1] (integrators.py:62-152); the higher-order
+    # ones (mclachlan / yoshida / omelyan) run through the general-coefficient kernels
+    integrators.check_supported(integrator, allow_general=True)
+    kick_c = integrator.coefficients[0::2]   # b1 .. b1
+    drift_c = integrator.coefficients[1::2]  # a1 ..
     if build_proposal is multinomial_hmc_proposal:
-        integrators.check_supported(integrator, allow_general=True)
-        return _build_mhmc_kernel(thr, integrator.coefficients[0::2], integrator.coefficients[1::2])
+        return _build_mhmc_kernel(thr, kick_c, drift_c)
     if build_proposal not in (None, hmc_proposal):
         raise NotImplementedError(
             "build_proposal must be hmc_proposal (default) or multinomial_hmc_proposal")
-    # any palindromic coefficient list [b1, a1, ..., b1] (integrators.py:62-152); the higher-order
-    # ones (mclachlan / yoshida / omelyan) run through the general-coefficient kernels (diag metric)
-    integrators.check_supported(integrator, allow_general=True)
     general = integrator is not integrators.velocity_verlet
-    kick_c = integrator.coefficients[0::2]   # b1 .. b1
-    drift_c = integrator.coefficients[1::2]  # a1 ..
     if chain_block is None:
         chain_block = _default_chain_block()
-    graphs: dict = {}
-    not_capturable: dict = {}    # id -> callable whose capture failed once ("auto" mode; the
-    #                              reference keeps the id from being reused by another object)
-    seen: dict = {}              # "auto" mode: calls per (shape, L, callable)
+    graphs = _GraphCache()
 
     def kernel(rng_key, state: HMCState, logdensity_fn: Callable, step_size,
                inverse_mass_matrix, num_integration_steps: int, *, chain_offset: int = 0):
-        """One HMC transition for all chains (hmc.py:279-312 + hmc_proposal.generate 153-176)."""
-        q0 = check_batch(state.position, "state.position")
-        logp0 = check_batch(state.logdensity, "state.logdensity")
-        g0 = check_batch(state.logdensity_grad, "state.logdensity_grad")
-        N, D = q0.shape
-        L = int(num_integration_steps)
-        if L < 0:
-            raise ValueError("num_integration_steps must be >= 0")
-        k0, k1, fold = key_spec(rng_key)
-        vg = value_and_grad(logdensity_fn)
-        metric = metrics.default_metric(inverse_mass_matrix, N, D, q0.device)
-        eps, eps_pc = step_size_args(step_size, N, q0.device)
-        stream = _lib.current_stream()
-        off = int(chain_offset)
-        dev = q0.device
-        graphed = use_graph is True and L >= 1 and metric.kind == "diag" and not general
-
-        p0 = torch.empty_like(q0)
-        ke0 = torch.empty_like(logp0)
-        p_end = torch.empty_like(q0)
-        q_new = torch.empty_like(q0)
-        g_new = torch.empty_like(q0)
-        logp_new = torch.empty_like(logp0)
-        acc_rate = torch.empty_like(logp0)
-        energy = torch.empty_like(logp0)
-        is_acc = torch.empty(N, dtype=torch.bool, device=dev)
-        is_div = torch.empty(N, dtype=torch.bool, device=dev)
-
-        cb = chain_block
-        n_streams = streams
-        if n_streams == "auto":
-            n_streams = 1
-        if cb == "auto":  # Infinity-Cache tiling pays for the streaming (diagonal) kernels only
-            if metric.kind == "diag":
-                cb = auto_chain_block(N, D, 3 + (1 if metric.imm_stride else 0))
-            elif metric.kind == "dense" and int(n_streams) > 1:
-                cb = -(-N // int(n_streams) // 128) * 128  # equal blocks of whole 128-row GEMM tiles
-            else:
-                cb = N
-        blk = N if not cb or cb >= N else int(cb)
-        n_blocks = (N + blk - 1) // blk if N else 0
-        fn_id = id(logdensity_fn)  # graphs are keyed on the USER's callable (and hold it)
-        if (use_graph == "auto" and L >= 2 and N > 0 and metric.kind == "diag" and not general
-                and blk * D <= (1 << 21) and is_capturable(logdensity_fn)
-                and fn_id not in not_capturable):
-            gkey = (min(blk, N), D, L, fn_id, metric.imm_stride != 0, dev.index)
-            # record on the SECOND call with a given shape and trajectory length (a one-off call --
-            # or a caller that varies L from step to step -- should not pay for a recording), and
-            # keep at most 8 recordings per kernel
-            seen[gkey] = seen.get(gkey, 0) + 1
-            try:
-                if gkey not in graphs and seen[gkey] >= 2 and len(graphs) < 8:
-                    graphs[gkey] = _GraphedTrajectory(min(blk, N), D, L, vg, metric.imm_stride != 0, dev,
-                                                      owner=logdensity_fn)
-                graphed = gkey in graphs
-            except RuntimeError:  # the callable cannot be recorded (or is broken: the plain path re-raises)
-                not_capturable[fn_id] = logdensity_fn
-                torch.cuda.synchronize(dev)
-        if (use_graph == "auto" and L >= 2 and N > 0 and metric.kind == "diag" and not general
-                and blk * D <= (1 << 21) and not is_capturable(logdensity_fn)):
-            warn_eager_driver(logdensity_fn, "hmc")  # small launches from Python: say so once
-        single = n_blocks <= 1 and not graphed
-        # end-of-trajectory state (HMCInfo.proposal): per-block work buffers are copied out
-        # unless the whole batch is one un-graphed block, in which case they ARE the result
-        q_end = torch.empty_like(q0) if L > 0 else q0
-        p_work = torch.empty_like(q0) if (L > 0 and not graphed) else None
-        # (a callable that evaluates into the caller's buffers writes g / logp of every block straight here, one
-        # un-graphed block included; the outputs of any other callable are copied in, or adopted when single)
-        writes_into = getattr(vg, "_bjx_eval_into", None) is not None
-        g_end = torch.empty_like(q0) if (L > 0 and (not single or writes_into)) else None
-        logp_end = torch.empty_like(logp0) if (L > 0 and (not single or writes_into)) else None
-        if L == 0:
-            g_end, logp_end = g0, logp0
-
-        def block_args(b):
-            s, e = b * blk, min(N, (b + 1) * blk)
-            sl = slice(s, e)
-            if metric.kind == "dense_pc":  # per-chain matrices travel with their chains
-                m = metric._replace(imm=metric.imm[sl], mass_sqrt_t=metric.mass_sqrt_t[sl])
-            else:
-                m = metric if metric.imm_stride == 0 else metric._replace(imm=metric.imm[sl])
-            return e - s, sl, m, (None if eps_pc is None else eps_pc[sl]), off + s
-
-        # plain velocity-Verlet trajectory on a diagonal metric with rows long enough for the row-per-wave
-        # momentum kernel: the first kick + drift ride along with the (RNG-bound) momentum draw
-        fused_first = (metric.kind == "diag" and L > 0 and not graphed and not general and D > 128 and _FUSE_FIRST)
-
-        def launch_first(b, stream_):
-            n, sl, m, eb, boff = block_args(b)
-            _lib.call("bjx_hmc_momentum_kick_diag", stream_, k0, k1, boff, fold, n, D, m.imm.data_ptr(),
-                      m.imm_stride, eps, _lib.ptr(eb), q0[sl].data_ptr(), g0[sl].data_ptr(),
-                      p0[sl].data_ptr(), ke0[sl].data_ptr(), q_end[sl].data_ptr(), p_work[sl].data_ptr())
-
-        def run_block(b):
-            """One chain block's transition as a generator: yields after every log-density
-            evaluation so that several blocks can be advanced in turn on their own streams."""
-            nonlocal g_end, logp_end
-            stream = _lib.current_stream()
-            n, sl, m, eb, boff = block_args(b)
-            # the block's ONE gradient buffer (and logp): its slice of the result arrays
-            if L > 0 and g_end is not None:
-                g_buf, logp_buf = (g_end, logp_end) if single else (g_end[sl], logp_end[sl])
-            else:
-                g_buf = logp_buf = None
-
-            def evaluate(q_, need_logp):
-                """One log-density evaluation of the trajectory; ``need_logp`` is true for the last one only."""
-                if g_buf is None:
-                    return eval_logdensity(vg, q_)
-                return eval_into(vg, q_, logp_buf, g_buf, need_logp)
-
-            if fused_first:
-                q, p = q_end[sl], p_work[sl]
-                launch_first(b, stream)
-            elif m.kind == "diag":
-                _lib.call("bjx_hmc_momentum_diag", stream, k0, k1, boff, fold, n, D, m.imm.data_ptr(),
-                          m.imm_stride, p0[sl].data_ptr(), ke0[sl].data_ptr())
-            else:
-                from . import dense
-
-                dense.momentum(stream, m, k0, k1, boff, fold, n, D, p0[sl], ke0[sl])
-
-            if L == 0:
-                q, p, logp, g = q0[sl], p0[sl], logp0[sl], g0[sl]
-                eps_fin, eps_pc_fin = 0.0, None
-            elif graphed:
-                gkey = (n, D, L, fn_id, m.imm_stride != 0, dev.index)
-                ctx = graphs.get(gkey)
-                if ctx is None:
-                    ctx = graphs[gkey] = _GraphedTrajectory(n, D, L, vg, m.imm_stride != 0, dev,
-                                                            owner=logdensity_fn)
-                if eb is None:
-                    ctx.eps.fill_(eps)
-                else:
-                    ctx.eps.copy_(eb)
-                ctx.imm.copy_(m.imm)
-                # first kick + drift writes straight into the static workspace
-                _launch_leapfrog(stream, m, n, D, 1, eps, eb, q0[sl], p0[sl], g0[sl], ctx.Wq, ctx.Wp)
-                ctx.graph.replay()
-                q, p, logp, g = ctx.Wq, ctx.Wp, ctx.logp, ctx.g
-                eps_fin, eps_pc_fin = eps, eb
-            elif general:
-                # generalized_two_stage_integrator (integrators.py:104-150): one launch per position
-                # update; the closing kick b_K of a step merges with the opening kick b_1 of the next
-                q, p = q_end[sl], p_work[sl]
-
-                def stage(n_k, ka, kb, a_c, q_in, p_in, g_in, p_out):
-                    if m.kind == "diag":
-                        _lib.call("bjx_leapfrog_diag_coef", stream, n, D, n_k, ka, kb, a_c, eps, _lib.ptr(eb),
-                                  m.imm.data_ptr(), m.imm_stride, q_in.data_ptr(), p_in.data_ptr(),
-                                  g_in.data_ptr(), q.data_ptr(), p_out.data_ptr(), None, 0)
-                        return p_out
-                    from . import dense
-
-                    return dense.leapfrog_coef(stream, m, n, D, n_k, ka, kb, a_c, eps, eb, q_in, p_in,
-                                               g_in, q, p_out)
-
-                first = True
-                logp = g = None
-                for i in range(L):
-                    for si, a_c in enumerate(drift_c):
-                        if first:
-                            p = stage(1, kick_c[0], 0.0, a_c, q0[sl], p0[sl], g0[sl], p)
-                            first = False
-                        elif si == 0:
-                            p = stage(2, kick_c[-1], kick_c[0], a_c, q, p, g, p)
-                        else:
-                            p = stage(1, kick_c[si], 0.0, a_c, q, p, g, p)
-                        del logp, g  # consumed: a callable that allocates its outputs gets the same block again
-                        logp, g = evaluate(q, i == L - 1 and si == len(drift_c) - 1)
-                        yield
-                        stream = _lib.current_stream()
-                eps_fin, eps_pc_fin = eps, eb
-            else:
-                if not fused_first:
-                    q, p = q_end[sl], p_work[sl]
-                    p = _launch_leapfrog(stream, m, n, D, 1, eps, eb, q0[sl], p0[sl], g0[sl], q, p)
-                logp, g = evaluate(q, L == 1)
-                for i in range(L - 1):
-                    yield
-                    stream = _lib.current_stream()
-                    p = _launch_leapfrog(stream, m, n, D, 2, eps, eb, q, p, g, q, p)
-                    # consumed: a callable that allocates its own outputs gets the same block back from the
-                    # (stream-ordered) allocator, so the block's working set stays q, p, g (3 arrays)
-                    del logp, g
-                    logp, g = evaluate(q, i == L - 2)
-                yield
-                stream = _lib.current_stream()
-                eps_fin, eps_pc_fin = eps, eb
-
-            if m.kind == "diag" and general:
-                _lib.call("bjx_hmc_finish_diag_coef", stream, k0, k1, boff, fold, n, D, kick_c[-1],
-                          eps_fin, _lib.ptr(eps_pc_fin), m.imm.data_ptr(), m.imm_stride, thr,
-                          q0[sl].data_ptr(), logp0[sl].data_ptr(), g0[sl].data_ptr(),
-                          ke0[sl].data_ptr(), q.data_ptr(), logp.data_ptr(), g.data_ptr(),
-                          p.data_ptr(), p_end[sl].data_ptr(), q_new[sl].data_ptr(),
-                          logp_new[sl].data_ptr(), g_new[sl].data_ptr(), acc_rate[sl].data_ptr(),
-                          is_acc[sl].data_ptr(), is_div[sl].data_ptr(), energy[sl].data_ptr())
-            elif m.kind == "diag":
-                _lib.call("bjx_hmc_finish_diag", stream, k0, k1, boff, fold, n, D, eps_fin,
-                          _lib.ptr(eps_pc_fin), m.imm.data_ptr(), m.imm_stride, thr,
-                          q0[sl].data_ptr(), logp0[sl].data_ptr(), g0[sl].data_ptr(),
-                          ke0[sl].data_ptr(), q.data_ptr(), logp.data_ptr(), g.data_ptr(),
-                          p.data_ptr(), p_end[sl].data_ptr(), q_new[sl].data_ptr(),
-                          logp_new[sl].data_ptr(), g_new[sl].data_ptr(), acc_rate[sl].data_ptr(),
-                          is_acc[sl].data_ptr(), is_div[sl].data_ptr(), energy[sl].data_ptr())
-            elif general:
-                from . import dense
-
-                dense.finish_coef(stream, m, k0, k1, boff, fold, n, D, kick_c[-1], eps_fin, eps_pc_fin, thr,
-                                  q0[sl], logp0[sl], g0[sl], ke0[sl], q, logp, g, p, p_end[sl], q_new[sl],
-                                  logp_new[sl], g_new[sl], acc_rate[sl], is_acc[sl], is_div[sl], energy[sl])
-            else:
-                from . import dense
-
-                dense.finish(stream, m, k0, k1, boff, fold, n, D, eps_fin, eps_pc_fin, thr, q0[sl],
-                             logp0[sl], g0[sl], ke0[sl], q, logp, g, p, p_end[sl], q_new[sl],
-                             logp_new[sl], g_new[sl], acc_rate[sl], is_acc[sl], is_div[sl],
-                             energy[sl])
-            if L > 0:
-                if g is g_buf:  # (and logp is logp_buf: the last evaluation is never gradient-only)
-                    pass        # the callable wrote the block's end state where it belongs
-                elif single:
-                    g_end, logp_end = g, logp
-                else:
-                    g_end[sl].copy_(g)
-                    logp_end[sl].copy_(logp)
-                if graphed:
-                    q_end[sl].copy_(q)
-
-
-        # Blocks are independent, so up to `n_streams` of them are advanced in turn, each on its own
-        # HIP stream: one block's callable (bandwidth-bound), the start-up of its launches and the
-        # output drain of a dense-metric GEMM then overlap another block's kernels.
-        ns = 1 if (graphed or n_blocks <= 1) else min(int(n_streams), n_blocks)
-        if ns <= 1:
-            for b in range(n_blocks):
-                for _ in run_block(b):
-                    pass
-        else:
-            main = torch.cuda.current_stream(dev)
-            pool = _side_streams(dev, ns)
-            for st_ in pool:
-                st_.wait_stream(main)
-            for w0 in range(0, n_blocks, ns):
-                active = [(run_block(b), pool[b - w0]) for b in range(w0, min(w0 + ns, n_blocks))]
-                while active:
-                    for item in list(active):
-                        with torch.cuda.stream(item[1]):
-                            try:
-                                next(item[0])
-                            except StopIteration:
-                                active.remove(item)
-            for st_ in pool:
-                main.wait_stream(st_)
-
-        if n_blocks == 0 and L > 0:
-            g_end, logp_end = g0, logp0
-        info = HMCInfo(p0, acc_rate, is_acc, is_div, energy,
-                       IntegratorState(q_end, p_end, logp_end, g_end), L)
-        return HMCState(q_new, logp_new, g_new), info
+        return _Transition(thr, general, kick_c, drift_c, chain_block, streams, use_graph, graphs, rng_key, state,
+                           logdensity_fn, step_size, inverse_mass_matrix, num_integration_steps, chain_offset).run()
 
     return kernel
 
@@ -637,13 +544,10 @@ def build_fused_target_kernel(divergence_threshold: float = 1000, *, with_info_a
 
     def kernel(rng_key, state: HMCState, logdensity_fn: Callable, step_size,
                inverse_mass_matrix, num_integration_steps: int, *, chain_offset: int = 0):
-        q0 = check_batch(state.position, "state.position")
-        logp0 = check_batch(state.logdensity, "state.logdensity")
-        g0 = check_batch(state.logdensity_grad, "state.logdensity_grad")
-        N, D = q0.shape
+        q0, logp0, g0, N, D, (k0, k1, fold), _, metric, eps, eps_pc, _, _ = _prologue(
+            rng_key, state, logdensity_fn, step_size, inverse_mass_matrix, chain_offset)
         dev = q0.device
         L = int(num_integration_steps)
-        metric = metrics.default_metric(inverse_mass_matrix, N, D, dev)
         spec = getattr(logdensity_fn, "_bjx_fused_target", None)
         spec = spec(D) if callable(spec) else None
         if spec is None or metric.kind != "diag" or D % 4 != 0 or not 128 < D <= 1024 or L < 1:
@@ -651,8 +555,6 @@ def build_fused_target_kernel(divergence_threshold: float = 1000, *, with_info_a
                 "fuse_target=True needs a blackjax_amd.targets log-density the engine can evaluate in place "
                 "(NealFunnel; DiagGaussian), a diagonal metric, 128 < D <= 1024 with D % 4 == 0 and at least "
                 "one integration step")
-        k0, k1, fold = key_spec(rng_key)
-        eps, eps_pc = step_size_args(step_size, N, dev)
         q_new, g_new, logp_new = torch.empty_like(q0), torch.empty_like(g0), torch.empty_like(logp0)
         acc_rate, energy = torch.empty_like(logp0), torch.empty_like(logp0)
         is_acc = torch.empty(N, dtype=torch.bool, device=dev)
