@@ -12,6 +12,7 @@ import functools as _functools
 from . import dynamic_hmc as _dynamic_hmc
 from . import ghmc as _ghmc
 from . import hmc as _hmc
+from . import mala as _mala
 from . import nuts as _nuts
 from . import adaptation, chees, diagnostics, distributed, integrators, meads, metrics, optim, random, rtc, targets, util
 from .adaptation import staged_adaptation, window_adaptation
@@ -62,5 +63,7 @@ dmhmc = GenerateSamplingAPI(
 hmc_family = [hmc, nuts, mhmc]  # blackjax/__init__.py:188
 # Generalized HMC (blackjax/mcmc/ghmc.py), the sampler the MEADS warm-up tunes
 ghmc = GenerateSamplingAPI(_ghmc.as_top_level_api, _ghmc.init, _ghmc.build_kernel)
+# Metropolis-adjusted Langevin (blackjax/mcmc/mala.py): one gradient per transition
+mala = GenerateSamplingAPI(_mala.as_top_level_api, _mala.init, _mala.build_kernel)
 
-__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]
+__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]

@@ -269,6 +269,13 @@ SIGNATURES.update({
     "bjx_ghmc_finish": [c_void_p, c_int64, c_int64, c_float, _f32p, _f32p, c_int64, c_float]
                        + [_f32p] * 12 + [c_int64, c_int64] + [_f32p] * 6 + [_u8p, _u8p, _f32p, _f32p],
 })
+# include/bjx_hip.h "MALA" (Metropolis-adjusted Langevin: proposal, asymmetric accept + select)
+SIGNATURES.update({
+    "bjx_mala_propose": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, _f32p,
+                         _f32p, _f32p, _f32p],
+    "bjx_mala_finish": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, _f32p]
+                       + [_f32p] * 10 + [_u8p],
+})
 SIGNATURES.update({
     "bjx_meads_fold_moments": [c_void_p, c_int64, c_int64, c_int64, _f32p, c_void_p, _f32p, _f32p, _f32p],
     "bjx_meads_fold_build": [c_void_p, c_int64, c_int64, c_int64, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,

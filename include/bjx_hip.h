@@ -458,6 +458,29 @@ int bjx_welford_final_diag(void* stream, int64_t N, int64_t D, int64_t sample_si
                            float imm_shrinkage_to_previous, const float* m2, const float* imm_prev,
                            int64_t imm_prev_stride, float* imm_out);
 
+/* ---- MALA (blackjax.mala; blackjax/mcmc/mala.py) --------------------------------------------
+ * One transition = bjx_mala_propose -> user callable at q1 -> bjx_mala_finish.  `tau` is the step size
+ * (scalar, or a device (N,) array `tau_per_chain` as with `eps`).  Keys as in bjx_hmc_finish_diag:
+ *   k_i = split(key, .)[chain_offset+i] (or its step_fold child) ; key_integrator, key_rmh = split(k_i, 2)
+ *
+ * Proposal: q1 = q0 + tau g0 + sqrt(2 tau) normal(key_integrator, (D,)), left to right, one fma per term.
+ * Replaces: mcmc/diffusions.py::overdamped_langevin (one_step) as called by mcmc/mala.py (kernel). */
+int bjx_mala_propose(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold,
+                     int64_t N, int64_t D, float tau, const float* tau_per_chain, const float* q0,
+                     const float* g0, float* q1_out);
+/* Asymmetric Metropolis-Hastings accept + state select, out of place:
+ *   E(a -> b) = -logp_b + (0.25 * (1 / tau)) * sum (q_a - q_b - tau g_b)^2      (transition_energy)
+ *   delta = E(q1 -> q0) - E(q0 -> q1) (NaN -> -inf) ; p_acc = min(1, exp(delta))
+ *   accept = uniform(key_rmh) < p_acc ; (q, logp, g)_out = accept ? (q1, logp1, g1) : (q0, logp0, g0)
+ * is_accepted_out: one byte per chain, 0 / 1.
+ * Replaces: mcmc/mala.py (transition_energy, kernel) ; mcmc/proposal.py::compute_asymmetric_acceptance_ratio,
+ * static_binomial_sampling, safe_energy_diff. */
+int bjx_mala_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold,
+                    int64_t N, int64_t D, float tau, const float* tau_per_chain, const float* q0,
+                    const float* logp0, const float* g0, const float* q1, const float* logp1, const float* g1,
+                    float* q_out, float* logp_out, float* g_out, float* acceptance_rate_out,
+                    uint8_t* is_accepted_out);
+
 /* Built-in synthetic targets (value + gradient in one pass, fp64-accumulated logp) used
  * as the "user callable" by the bench and parity tests.
  *   diag gaussian:  g = -(q*inv_var) ; logp = 0.5 * sum q*g     (tests/fixtures.py:60-78)
