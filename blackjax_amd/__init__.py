@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import functools as _functools
 
+from . import barker as _barker
 from . import dynamic_hmc as _dynamic_hmc
 from . import ghmc as _ghmc
 from . import hmc as _hmc
@@ -65,5 +66,9 @@ hmc_family = [hmc, nuts, mhmc]  # blackjax/__init__.py:188
 ghmc = GenerateSamplingAPI(_ghmc.as_top_level_api, _ghmc.init, _ghmc.build_kernel)
 # Metropolis-adjusted Langevin (blackjax/mcmc/mala.py): one gradient per transition
 mala = GenerateSamplingAPI(_mala.as_top_level_api, _mala.init, _mala.build_kernel)
+# Barker proposal (blackjax/mcmc/barker.py, exported by the reference as barker_proposal): one gradient per
+# transition, step size and diagonal metric tuned by window_adaptation
+barker = GenerateSamplingAPI(_barker.as_top_level_api, _barker.init, _barker.build_kernel)
+barker_proposal = barker
 
-__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]
+__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "barker", "barker_proposal", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]

@@ -276,6 +276,13 @@ SIGNATURES.update({
     "bjx_mala_finish": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, _f32p]
                        + [_f32p] * 10 + [_u8p],
 })
+# include/bjx_hip.h "Barker" (Barker proposal: per-element signed step, asymmetric accept + select)
+SIGNATURES.update({
+    "bjx_barker_propose": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, _f32p,
+                           _f32p, c_int64, _f32p, _f32p, _f32p],
+    "bjx_barker_finish": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64] + [_f32p] * 10
+                         + [_u8p],
+})
 SIGNATURES.update({
     "bjx_meads_fold_moments": [c_void_p, c_int64, c_int64, c_int64, _f32p, c_void_p, _f32p, _f32p, _f32p],
     "bjx_meads_fold_build": [c_void_p, c_int64, c_int64, c_int64, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,

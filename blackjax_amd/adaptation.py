@@ -299,9 +299,12 @@ def window_adaptation(algorithm, logdensity_fn: Callable, is_mass_matrix_diagona
                       adaptation_info_fn: Optional[Callable] = _default_adapt_info,
                       integrator=integrators.velocity_verlet, _schedule_fn: Optional[Callable] = None,
                       fuse_target: bool = False, **extra_parameters) -> AdaptationAlgorithm:
-    """blackjax/adaptation/window_adaptation.py:296-444.  ``algorithm`` is ``blackjax_amd.hmc`` or
-    ``blackjax_amd.nuts``; ``extra_parameters`` are forwarded to its kernel (e.g.
+    """blackjax/adaptation/window_adaptation.py:296-444.  ``algorithm`` is ``blackjax_amd.hmc``,
+    ``blackjax_amd.nuts`` or ``blackjax_amd.barker``; ``extra_parameters`` are forwarded to its kernel (e.g.
     ``num_integration_steps=...``).  ``adaptation_info_fn=None`` records nothing.
+
+    ``blackjax_amd.barker`` (no integrator, diagonal metric only): the default ``target_acceptance_rate`` stays
+    0.80 as for every algorithm; about 0.4 is the usual target for the Barker proposal, so pass it.
 
     ``run(rng_key, position, num_steps)`` returns ``(AdaptationResults, AdaptationInfo)`` as in the
     reference.  ``run(..., free_running=True)`` (NUTS, diagonal metric, default integrator) returns
@@ -330,7 +333,18 @@ def window_adaptation(algorithm, logdensity_fn: Callable, is_mass_matrix_diagona
     if imm_shrinkage_to_previous < 0.0:
         raise ValueError(
             f"imm_shrinkage_to_previous must be >= 0.0, got {imm_shrinkage_to_previous}")
-    mcmc_kernel = algorithm.build_kernel(integrator)  # the sampler validates the integrator
+    from .barker import build_kernel as _barker_build_kernel
+
+    if getattr(algorithm, "build_kernel", None) is _barker_build_kernel:
+        # no integrator: the kernel takes (rng_key, state, logdensity_fn, step_size, inverse_mass_matrix) as it is
+        if integrator is not integrators.velocity_verlet:
+            raise ValueError("window_adaptation(blackjax_amd.barker): the Barker proposal has no integrator")
+        if not is_mass_matrix_diagonal:
+            raise NotImplementedError("window_adaptation(blackjax_amd.barker): a diagonal mass matrix only "
+                                      "(is_mass_matrix_diagonal=True); dense preconditioning is not implemented")
+        mcmc_kernel = algorithm.build_kernel()
+    else:
+        mcmc_kernel = algorithm.build_kernel(integrator)  # the sampler validates the integrator
     step_extra = extra_parameters  # what every step of the kernel receives
     if fuse_target:
         from .hmc import build_fused_target_kernel as _fused, build_kernel as _hmc_build_kernel

@@ -481,6 +481,32 @@ int bjx_mala_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_of
                     float* q_out, float* logp_out, float* g_out, float* acceptance_rate_out,
                     uint8_t* is_accepted_out);
 
+/* ---- Barker (blackjax.barker_proposal; blackjax/mcmc/barker.py) ------------------------------
+ * One transition = bjx_barker_propose -> user callable at q1 -> bjx_barker_finish.  `tau` as for MALA.  `imm` is a
+ * diagonal inverse mass matrix: null = ones, (D,) with imm_row_stride 0, or (N, D) with imm_row_stride D.  Keys:
+ *   k_i = split(key, .)[chain_offset+i] (or its step_fold child) ; key_sample, key_rmh = split(k_i, 2) ;
+ *   k1, k2 = split(key_sample, 2)
+ *
+ * Proposal, per element d (each product one fp32 rounding, expit in fp64 rounded once):
+ *   z = (tau * sqrtf(imm[d])) * normal(k1, (D,))[d] ; p = expit(z * g0[d]) ; b = uniform(k2, (D,))[d] < p
+ *   q1[d] = b ? q0[d] + z : q0[d] - z          (a NaN p compares false)
+ * Replaces: mcmc/barker.py::_barker_sample_nd as called by its kernel, diagonal preconditioner. */
+int bjx_barker_propose(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold,
+                       int64_t N, int64_t D, float tau, const float* tau_per_chain, const float* imm,
+                       int64_t imm_row_stride, const float* q0, const float* g0, float* q1_out);
+/* Asymmetric Metropolis-Hastings accept + state select, out of place.  With t = q1 - q0 (the diagonal scale
+ * cancels, so neither tau nor imm is needed) and softplus(x) = max(x, 0) + log1p(exp(-|x|)) in fp64:
+ *   S = sum_d softplus(-(t g0)) - softplus(t g1)   (fp64 sum, rounded once)
+ *   log_ratio = (logp1 - logp0) + S (NaN -> -inf) ; p_acc = min(1, exp(log_ratio))
+ *   accept = uniform(key_rmh) < p_acc ; (q, logp, g)_out = accept ? (q1, logp1, g1) : (q0, logp0, g0)
+ * is_accepted_out: one byte per chain, 0 / 1.
+ * Replaces: mcmc/barker.py (_barker_logpdf, kernel) ; mcmc/proposal.py::compute_asymmetric_acceptance_ratio,
+ * static_binomial_sampling, safe_energy_diff. */
+int bjx_barker_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold,
+                      int64_t N, int64_t D, const float* q0, const float* logp0, const float* g0,
+                      const float* q1, const float* logp1, const float* g1, float* q_out, float* logp_out,
+                      float* g_out, float* acceptance_rate_out, uint8_t* is_accepted_out);
+
 /* Built-in synthetic targets (value + gradient in one pass, fp64-accumulated logp) used
  * as the "user callable" by the bench and parity tests.
  *   diag gaussian:  g = -(q*inv_var) ; logp = 0.5 * sum q*g     (tests/fixtures.py:60-78)
