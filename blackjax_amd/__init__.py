@@ -11,6 +11,7 @@ import functools as _functools
 
 from . import barker as _barker
 from . import dynamic_hmc as _dynamic_hmc
+from . import elliptical_slice as _elliptical_slice
 from . import ghmc as _ghmc
 from . import hmc as _hmc
 from . import mala as _mala
@@ -70,5 +71,8 @@ mala = GenerateSamplingAPI(_mala.as_top_level_api, _mala.init, _mala.build_kerne
 # transition, step size and diagonal metric tuned by window_adaptation
 barker = GenerateSamplingAPI(_barker.as_top_level_api, _barker.init, _barker.build_kernel)
 barker_proposal = barker
+# Elliptical slice sampling (blackjax/mcmc/elliptical_slice.py): Gaussian prior, value-only log-likelihood, no gradient
+elliptical_slice = GenerateSamplingAPI(_elliptical_slice.as_top_level_api, _elliptical_slice.init,
+                                       _elliptical_slice.build_kernel)
 
-__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "barker", "barker_proposal", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]
+__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "barker", "barker_proposal", "elliptical_slice", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]

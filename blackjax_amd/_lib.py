@@ -283,6 +283,15 @@ SIGNATURES.update({
     "bjx_barker_finish": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64] + [_f32p] * 10
                          + [_u8p],
 })
+# include/bjx_hip.h "elliptical slice" (Gaussian prior, value-only likelihood: opening, noise for the dense prior,
+# one round of the shrinking loop)
+SIGNATURES.update({
+    "bjx_ess_begin": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64] + [_f32p] * 11
+                     + [c_void_p, _u8p],
+    "bjx_ess_noise": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, _f32p],
+    "bjx_ess_shrink": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64] + [_f32p] * 8
+                      + [c_void_p, _u8p] + [_f32p] * 3 + [c_void_p, _f32p, c_void_p],
+})
 SIGNATURES.update({
     "bjx_meads_fold_moments": [c_void_p, c_int64, c_int64, c_int64, _f32p, c_void_p, _f32p, _f32p, _f32p],
     "bjx_meads_fold_build": [c_void_p, c_int64, c_int64, c_int64, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p,

@@ -507,6 +507,44 @@ int bjx_barker_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_
                       const float* q1, const float* logp1, const float* g1, float* q_out, float* logp_out,
                       float* g_out, float* acceptance_rate_out, uint8_t* is_accepted_out);
 
+/* ---- elliptical slice (blackjax.elliptical_slice; blackjax/mcmc/elliptical_slice.py) ----------
+ * Gaussian prior N(mean, cov) shared by all chains, arbitrary log-LIKELIHOOD (value only, no gradient).  One
+ * transition = bjx_ess_begin -> user callable at q_prop -> { bjx_ess_shrink -> user callable at q_prop } until
+ * bjx_ess_shrink leaves *n_live == 0.  Keys:
+ *   k_i = split(key, .)[chain_offset+i] (or its step_fold child) ;
+ *   key_slice, key_momentum, key_uniform, key_theta = split(k_i, 4)
+ * With c, s = cos, sin of (double)theta, each rounded once, a = q0 - mean and b = nu - mean:
+ *   p(theta) = fma(b, s, a * c) + mean ;  m(theta) = fma(-a, s, b * c) + mean            (ellipsis)
+ *
+ * bjx_ess_begin: exactly one of cov_diag (D,) and nu_lin (N, D) is given.
+ *   nu = fma(sqrtf(cov_diag[j]), normal(key_momentum, (D,))[j], mean[j])                 (diagonal prior)
+ *   nu = nu_lin + mean, nu_lin = normal(key_momentum, (D,)) @ L^T from bjx_ess_noise + bjx_dense_matmul   (dense)
+ *   logy = logp0 + log(uniform(key_uniform))   (fp64 log rounded once; u = 0 gives -inf)
+ *   theta = f32(2 pi) * uniform(key_theta) ; theta_min = theta - f32(2 pi) ; theta_max = theta
+ *   q_prop = p(theta) ; subiter = 1 ; done = 0
+ * Replaces: mcmc/elliptical_slice.py (kernel, elliptical_proposal up to its while_loop), util.py::generate_gaussian_noise. */
+int bjx_ess_begin(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int64_t N,
+                  int64_t D, const float* mean, const float* cov_diag, const float* nu_lin, const float* q0,
+                  const float* logp0, float* nu_out, float* q_prop_out, float* logy_out, float* theta_out,
+                  float* theta_min_out, float* theta_max_out, int32_t* subiter_out, uint8_t* done_out);
+/* n_out[i] = normal(key_momentum of chain i, (D,)): the left operand of the dense prior's product. */
+int bjx_ess_noise(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int64_t N,
+                  int64_t D, float* n_out);
+/* One round of the reference's while_loop (slice_fn), given logp_prop = log-likelihood of every q_prop row.  Per row:
+ *   done set: skipped (one byte read).
+ *   !(logp_prop <= logy) (a NaN ends the loop, as in the reference): logdensity_out = logp_prop, theta_out = theta,
+ *     subiter_out = subiter, momentum_out = m(theta), done = 1.  The q_prop row is the chain's new position and is
+ *     not written again.
+ *   otherwise: theta = max(theta_min, fma(unit_float(bits), theta_max - theta_min, theta_min)), bits from
+ *     fold_in(key_slice, subiter) ; q_prop = p(theta) ; theta_min = theta if theta < 0 ; theta_max = theta if
+ *     theta > 0 ; subiter += 1 ; *n_live += 1 (one atomic per row).
+ * The caller zeroes *n_live on the stream before the launch; there is no cap on the number of rounds here. */
+int bjx_ess_shrink(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int64_t N,
+                   int64_t D, const float* mean, const float* q0, const float* nu, const float* logp_prop,
+                   const float* logy, float* theta, float* theta_min, float* theta_max, int32_t* subiter,
+                   uint8_t* done, float* q_prop, float* logdensity_out, float* theta_out, int32_t* subiter_out,
+                   float* momentum_out, int32_t* n_live);
+
 /* Built-in synthetic targets (value + gradient in one pass, fp64-accumulated logp) used
  * as the "user callable" by the bench and parity tests.
  *   diag gaussian:  g = -(q*inv_var) ; logp = 0.5 * sum q*g     (tests/fixtures.py:60-78)
