@@ -299,8 +299,20 @@ SIGNATURES.update({
     "bjx_meads_fold_params": [c_void_p, c_int64, c_int64, c_int64, c_int64, c_float, c_float, c_int64, _f32p,
                               c_void_p, _f32p, c_void_p] + [_f32p] * 8,
 })
+# include/bjx_hip.h "SMC" (fixed-point resampling, row gather, tempered log-density, reweighting, ESS bisection;
+# bjx_smc_scan_tile returns the scan's tile size, not a status)
+SIGNATURES.update({
+    "bjx_smc_scan_tile": [],
+    "bjx_smc_resample": [c_void_p, c_uint32, c_uint32, ctypes.c_int32, c_int64, c_int64, _f32p, c_void_p, c_void_p],
+    "bjx_smc_gather": [c_void_p, c_int64, c_int64, c_int64, _f32p, c_void_p, _f32p],
+    "bjx_smc_temper": [c_void_p, c_int64, c_int64] + [_f32p] * 7,
+    "bjx_smc_reweight": [c_void_p, c_int64] + [_f32p] * 6,
+    "bjx_smc_log_ess": [c_void_p, c_int64, _f32p, _f32p],
+    "bjx_smc_ess_solve": [c_void_p, c_int64, _f32p, c_float, _f32p, _f32p, _f32p, _f32p],
+})
 INT64_FUNCTIONS = {"bjx_pool_workspace_bytes": [c_int64, c_int64],
-                   "bjx_meads_workspace_bytes": [c_int64, c_int64]}
+                   "bjx_meads_workspace_bytes": [c_int64, c_int64],
+                   "bjx_smc_resample_workspace_bytes": [c_int64]}
 
 _lib = None
 

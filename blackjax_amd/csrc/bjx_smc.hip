@@ -1,0 +1,422 @@
+// Sequential Monte Carlo arithmetic (gfx950).  C ABI in include/bjx_hip.h ("SMC").
+//
+// Reference: blackjax/smc/base.py (step), smc/resampling.py (systematic, stratified: _systematic_or_stratified,
+// _sorted_uniforms' callers), smc/ess.py (log_ess, ess_solver), smc/solver.py (dichotomy),
+// smc/tempered.py (build_kernel: log_weights_fn, tempered_logposterior_fn).
+//
+// Resampling works on cumulative weights in 2^-62 fixed point: integer addition is associative, so the prefix sum
+// is the same whatever the tiling, and the ancestor search compares integers.  The scan is launch-separated (tile
+// sums -> scan of the tile sums -> apply): no workgroup ever waits on another.  The log-sum-exp reweighting and the
+// ESS bisection are one workgroup each, looping over the (N,) log-likelihoods with fp64 sums: the number of
+// launches does not depend on the data and nothing is read back by the host.
+#include <math.h>
+
+#include "../../include/bjx_hip.h"
+#include "bjx_device.h"
+#include "bjx_host.h"
+
+using namespace bjx;
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
+constexpr int kScanItems = 4;                    // consecutive items per thread
+constexpr int kScanTile = kBlock * kScanItems;   // 1024 items per workgroup
+constexpr int kRedBlock = 1024;                  // the one workgroup of the reweight / ESS kernels
+constexpr int kRedWaves = kRedBlock / BJX_WAVE;
+constexpr int64_t kMaxParticles = (int64_t)1 << 24;  // positions are formed in fp32
+constexpr double kTwo62 = 4611686018427387904.0;
+constexpr int kHalvings = 30;
+
+// wf = (int64) floor((double) w * 2^62); anything that is not a weight in (0, 1] is clamped so that the sum of at
+// most 2^24 of them cannot leave int64 by more than a wrap the search survives (ancestors are clipped to [0, N)).
+__device__ __forceinline__ int64_t scan_item(const float* in, int64_t i) {
+  float w = in[i];
+  if (!(w > 0.0f)) return 0;  // zero, negative, NaN
+  if (w > 1.0f) w = 1.0f;
+  return (int64_t)floor((double)w * kTwo62);
+}
+__device__ __forceinline__ int64_t scan_item(const int64_t* in, int64_t i) { return in[i]; }
+
+// Inclusive prefix sum of one value per thread over the 256 threads of a workgroup; *total = the tile's sum.
+__device__ __forceinline__ int64_t block_scan_inclusive(int64_t v, int64_t* sh, int64_t* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long t = __shfl_up((long long)v, o, 64);
+    if (lane >= o) v += (int64_t)t;
+  }
+  if (lane == 63) sh[wave] = v;
+  __syncthreads();
+  int64_t base = 0, all = 0;
+#pragma unroll
+  for (int k = 0; k < kWavesPerBlock; ++k) {
+    if (k < wave) base += sh[k];
+    all += sh[k];
+  }
+  __syncthreads();
+  *total = all;
+  return v + base;
+}
+
+// Level 1 of the launch-separated scan: sums[b] = sum of tile b.
+template <typename In>
+__global__ void __launch_bounds__(kBlock) k_tile_sums(const In* in, int64_t n, int64_t* sums) {
+  __shared__ int64_t sh[kWavesPerBlock];
+  const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
+  int64_t s = 0;
+#pragma unroll
+  for (int e = 0; e < kScanItems; ++e)
+    if (i0 + e < n) s += scan_item(in, i0 + e);
+  int64_t total;
+  block_scan_inclusive(s, sh, &total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// Level 3: out[i] = tile_offsets[b - 1] + inclusive prefix inside tile b.  `tile_offsets` (null for a single tile)
+// holds the INCLUSIVE scan of the tile sums.  A thread reads only the items it writes, so in == out is allowed.
+template <typename In>
+__global__ void __launch_bounds__(kBlock) k_tile_scan(const In* in, int64_t n, const int64_t* tile_offsets,
+                                                      int64_t* out) {
+  __shared__ int64_t sh[kWavesPerBlock];
+  const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
+  int64_t v[kScanItems];
+  int64_t s = 0;
+#pragma unroll
+  for (int e = 0; e < kScanItems; ++e) {
+    v[e] = (i0 + e < n) ? scan_item(in, i0 + e) : 0;
+    s += v[e];
+    v[e] = s;
+  }
+  int64_t total;
+  const int64_t incl = block_scan_inclusive(s, sh, &total);
+  const int64_t base = (incl - s) + ((tile_offsets && blockIdx.x > 0) ? tile_offsets[blockIdx.x - 1] : 0);
+#pragma unroll
+  for (int e = 0; e < kScanItems; ++e)
+    if (i0 + e < n) out[i0 + e] = base + v[e];
+}
+
+// resampling.py::systematic / stratified: pos_i = (i + u_i) / M in fp32, u_i = uniform(key, ()) for every i
+// (systematic) or uniform(key, (M,))[i] (stratified); ancestor_i = min(N - 1, #{j : C_j < t_i}) with
+// t_i = (int64)(pos_i * 2^62), exact in fp64 -- searchsorted(cumsum(w), pos) and the reference's clip.
+template <bool STRATIFIED>
+__global__ void __launch_bounds__(kBlock)
+k_resample(Key key, int64_t N, int64_t M, const int64_t* __restrict__ cum, int32_t* __restrict__ ancestors) {
+  const float u_sys = key_uniform(key);
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += (int64_t)gridDim.x * kBlock) {
+    const float u = STRATIFIED ? fmaxf(0.0f, unit_float(key_bits32(key, (uint64_t)i))) : u_sys;
+    const float pos = ((float)i + u) / (float)M;
+    const int64_t t = (int64_t)((double)pos * kTwo62);
+    int64_t lo = 0, hi = N;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (cum[mid] < t) lo = mid + 1;
+      else hi = mid;
+    }
+    ancestors[i] = (int32_t)(lo < N - 1 ? lo : N - 1);
+  }
+}
+
+// out[i, :] = x[ancestors[i], :], one wavefront per output row, 16 bytes (VEC = 4) or 4 bytes per lane.  An index
+// outside [0, N) is clamped: the launch stays inside x whatever it is given.
+template <int VEC>
+__global__ void __launch_bounds__(kBlock)
+k_gather(int64_t N, int64_t M, int64_t D, const float* __restrict__ x, const int32_t* __restrict__ ancestors,
+         float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
+  for (int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); r < M; r += stride) {
+    int64_t a = ancestors[r];
+    a = a < 0 ? 0 : (a > N - 1 ? N - 1 : a);
+    const float* src = x + a * D;
+    float* dst = out + r * D;
+    for (int64_t j = (int64_t)lane * VEC; j < D; j += 64 * VEC) {
+      if constexpr (VEC == 4) st4(dst + j, ld4(src + j));
+      else dst[j] = src[j];
+    }
+  }
+}
+
+// tempered.py::tempered_logposterior_fn and its gradient: lp + lam * ll and gp + lam * gl, the product rounded
+// before the sum (no fmaf: NumPy reproduces both bit for bit).  lam is read from device memory, so one recorded
+// or traced launch serves every temperature.
+template <int VEC>
+__global__ void __launch_bounds__(kBlock)
+k_temper(int64_t N, int64_t D, const float* __restrict__ lam_p, const float* __restrict__ lp,
+         const float* __restrict__ gp, const float* __restrict__ ll, const float* __restrict__ gl,
+         float* __restrict__ lp_out, float* __restrict__ g_out) {
+  const float lam = *lam_p;
+  const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x, nthr = (int64_t)gridDim.x * kBlock;
+  const int64_t total = N * D;
+  for (int64_t i = tid * VEC; i < total; i += nthr * VEC) {
+    if constexpr (VEC == 4) {
+      const F4 a = ld4(gp + i), b = ld4(gl + i);
+      const float tx = lam * b.x, ty = lam * b.y, tz = lam * b.z, tw = lam * b.w;
+      st4(g_out + i, F4{a.x + tx, a.y + ty, a.z + tz, a.w + tw});
+    } else {
+      const float t = lam * gl[i];
+      g_out[i] = gp[i] + t;
+    }
+  }
+  for (int64_t i = tid; i < N; i += nthr) {
+    const float t = lam * ll[i];
+    lp_out[i] = lp[i] + t;
+  }
+}
+
+// ---- one-workgroup reductions over (N,) -------------------------------------------------------------------
+__device__ __forceinline__ double block_sum(double v, double* sh) {
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = 0.0;
+#pragma unroll
+  for (int k = 0; k < kRedWaves; ++k) t += sh[k];
+  __syncthreads();
+  return t;
+}
+
+__device__ __forceinline__ float block_max(float v, float* sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float t = sh[0];
+#pragma unroll
+  for (int k = 1; k < kRedWaves; ++k) t = fmaxf(t, sh[k]);
+  __syncthreads();
+  return t;
+}
+
+// tempered.py::log_weights_fn: delta * loglikelihood; delta == 0 gives 0 whatever ll is (the reference's
+// nan_to_num of 0 * inf).  A NaN or -inf log-weight is a particle of weight 0 and takes no part in any sum.
+__device__ __forceinline__ float log_weight(float delta, float ll) { return delta == 0.0f ? 0.0f : delta * ll; }
+__device__ __forceinline__ bool lw_counts(float lw) { return lw == lw && lw != -__builtin_inff(); }
+
+// base.py::step, the weighting: lw = (lam_new - lam_old) * ll ; lse = logsumexp(lw) ; w = exp(lw - lse) ;
+// log_likelihood_increment = lse - log N.  exp and log in fp64, the sum in fp64, each result rounded once.
+__global__ void __launch_bounds__(kRedBlock)
+k_reweight(int64_t N, const float* __restrict__ ll, const float* __restrict__ lam_old_p,
+           const float* __restrict__ lam_new_p, float* __restrict__ w_out, float* __restrict__ inc_out,
+           float* __restrict__ lam_out) {
+  __shared__ double shd[kRedWaves];
+  __shared__ float shf[kRedWaves];
+  const float lam_new = *lam_new_p;
+  const float delta = lam_new - *lam_old_p;
+  float m = -__builtin_inff();
+  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
+    const float lw = log_weight(delta, ll[j]);
+    if (lw_counts(lw)) m = fmaxf(m, lw);
+  }
+  m = block_max(m, shf);
+  double s = 0.0;
+  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
+    const float lw = log_weight(delta, ll[j]);
+    if (lw_counts(lw)) s += exp((double)lw - (double)m);
+  }
+  s = block_sum(s, shd);
+  const bool none = m == -__builtin_inff();  // no particle of positive weight: weights NaN, increment -inf
+  const double lse = none ? -(double)__builtin_inff() : (double)m + log(s);
+  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
+    const float lw = log_weight(delta, ll[j]);
+    w_out[j] = none ? __builtin_nanf("") : (lw_counts(lw) ? (float)exp((double)lw - lse) : 0.0f);
+  }
+  if (threadIdx.x == 0) {
+    *inc_out = (float)(lse - log((double)N));
+    *lam_out = lam_new;
+  }
+}
+
+// ess.py::log_ess = 2 logsumexp(lw) - logsumexp(2 lw) = 2 log S1 - log S2 with S_k = sum exp(k (lw - max)).
+__global__ void __launch_bounds__(kRedBlock)
+k_log_ess(int64_t N, const float* __restrict__ lw_in, float* __restrict__ out) {
+  __shared__ double shd[kRedWaves];
+  __shared__ float shf[kRedWaves];
+  float m = -__builtin_inff();
+  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
+    const float lw = lw_in[j];
+    if (lw_counts(lw)) m = fmaxf(m, lw);
+  }
+  m = block_max(m, shf);
+  double s1 = 0.0, s2 = 0.0;
+  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
+    const float lw = lw_in[j];
+    if (lw_counts(lw)) {
+      const double e = exp((double)lw - (double)m);
+      s1 += e;
+      s2 += e * e;
+    }
+  }
+  s1 = block_sum(s1, shd);
+  s2 = block_sum(s2, shd);
+  if (threadIdx.x == 0) *out = (float)(2.0 * log(s1) - log(s2));
+}
+
+// ess.py::ess_solver with solver.py::dichotomy, entirely on the device: f(d) = log_ess(d * ll) - log(N target).
+// f(max_delta) >= 0: delta = max_delta (and lam_new exactly 1 when max_delta is 1 - lam_old).  Otherwise 30
+// halvings of [0, max_delta] in fp32 that move the LEFT end to mid whenever f(mid) >= 0 and return the left end:
+// the ESS at the returned delta is never below the target.  max(d * ll) = d * max(ll) for d >= 0 (rounding is
+// monotone), so every evaluation of f is one sweep: e = exp(d * ll - d * ll_max) per particle in fp64 (an fp32
+// exponential would blur f by 1e-7, a hundred bisection widths), summed (and squared and summed) in fp64.
+__global__ void __launch_bounds__(kRedBlock)
+k_ess_solve(int64_t N, const float* __restrict__ ll, double log_target, const float* __restrict__ max_delta_p,
+            const float* __restrict__ lam_old_p, float* __restrict__ delta_out, float* __restrict__ lam_new_out) {
+  __shared__ double shd[kRedWaves];
+  __shared__ float shf[kRedWaves];
+  const float lam_old = lam_old_p ? *lam_old_p : 0.0f;
+  const float max_delta = max_delta_p ? *max_delta_p : 1.0f - lam_old;
+  float ll_max = -__builtin_inff();
+  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
+    const float v = ll[j];
+    if (lw_counts(v)) ll_max = fmaxf(ll_max, v);
+  }
+  ll_max = block_max(ll_max, shf);
+
+  auto f = [&](float d) -> double {
+    const float m = log_weight(d, ll_max);
+    double s1 = 0.0, s2 = 0.0;
+    for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
+      const float lw = log_weight(d, ll[j]);
+      if (lw_counts(lw)) {
+        const double e = exp((double)lw - (double)m);
+        s1 += e;
+        s2 += e * e;
+      }
+    }
+    s1 = block_sum(s1, shd);
+    s2 = block_sum(s2, shd);
+    return 2.0 * log(s1) - log(s2) - log_target;
+  };
+
+  float delta;
+  bool full = false;
+  if (f(max_delta) >= 0.0) {
+    delta = max_delta;
+    full = true;
+  } else {
+    float lo = 0.0f, hi = max_delta;
+    for (int it = 0; it < kHalvings; ++it) {
+      const float mid = 0.5f * (lo + hi);
+      if (f(mid) >= 0.0) lo = mid;  // (a NaN keeps the left end)
+      else hi = mid;
+    }
+    delta = lo;
+  }
+  if (threadIdx.x == 0) {
+    *delta_out = delta;
+    if (lam_new_out) *lam_new_out = (full && !max_delta_p) ? 1.0f : lam_old + delta;
+  }
+}
+
+unsigned flat_grid(int64_t n_items) {
+  const int64_t b = (n_items + kBlock - 1) / kBlock;
+  return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
+}
+
+int64_t n_tiles(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
+
+// Inclusive scan of n items into out; ws holds the tile sums of this level and of every level above it.
+template <typename In>
+void scan_level(hipStream_t stream, const In* in, int64_t n, int64_t* out, int64_t* ws) {
+  const int64_t nt = n_tiles(n);
+  if (nt == 1) {
+    hipLaunchKernelGGL(k_tile_scan<In>, dim3(1), dim3(kBlock), 0, stream, in, n, (const int64_t*)nullptr, out);
+    return;
+  }
+  hipLaunchKernelGGL(k_tile_sums<In>, dim3((unsigned)nt), dim3(kBlock), 0, stream, in, n, ws);
+  scan_level<int64_t>(stream, ws, nt, ws, ws + nt);
+  hipLaunchKernelGGL(k_tile_scan<In>, dim3((unsigned)nt), dim3(kBlock), 0, stream, in, n, (const int64_t*)ws, out);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bjx_smc_scan_tile(void) { return kScanTile; }
+
+int64_t bjx_smc_resample_workspace_bytes(int64_t N) {
+  if (N < 1 || N > kMaxParticles) return 0;
+  int64_t words = N;  // the cumulative weights, then the tile sums of every level
+  for (int64_t n = N; n_tiles(n) > 1; n = n_tiles(n)) words += n_tiles(n);
+  return words * (int64_t)sizeof(int64_t);
+}
+
+int bjx_smc_resample(void* stream, uint32_t key0, uint32_t key1, int32_t stratified, int64_t N,
+                     int64_t num_samples, const float* weights, int64_t* workspace, int32_t* ancestors_out) {
+  BJX_CHECK_ARG(N >= 1 && N <= kMaxParticles && num_samples >= 0 && num_samples <= kMaxParticles,
+                "bjx_smc_resample: bad sizes");
+  if (num_samples == 0) return 0;
+  BJX_CHECK_ARG(weights && workspace && ancestors_out, "bjx_smc_resample: null pointer");
+  const hipStream_t s = (hipStream_t)stream;
+  scan_level<float>(s, weights, N, workspace, workspace + N);
+  const Key key{key0, key1};
+  const dim3 grid(flat_grid(num_samples)), block(kBlock);
+  if (stratified)
+    hipLaunchKernelGGL(k_resample<true>, grid, block, 0, s, key, N, num_samples, (const int64_t*)workspace,
+                       ancestors_out);
+  else
+    hipLaunchKernelGGL(k_resample<false>, grid, block, 0, s, key, N, num_samples, (const int64_t*)workspace,
+                       ancestors_out);
+  return bjx_check_launch("bjx_smc_resample");
+}
+
+int bjx_smc_gather(void* stream, int64_t N, int64_t num_samples, int64_t D, const float* x,
+                   const int32_t* ancestors, float* out) {
+  BJX_CHECK_ARG(N >= 1 && num_samples >= 0 && D > 0, "bjx_smc_gather: bad sizes");
+  if (num_samples == 0) return 0;
+  BJX_CHECK_ARG(x && ancestors && out, "bjx_smc_gather: null pointer");
+  BJX_CHECK_ARG(x != out, "bjx_smc_gather: out of place only");
+  const dim3 grid(bjx_row_grid(num_samples, kWavesPerBlock)), block(kBlock);
+  if (bjx_vec4_ok(D, x, out))
+    hipLaunchKernelGGL(k_gather<4>, grid, block, 0, (hipStream_t)stream, N, num_samples, D, x, ancestors, out);
+  else
+    hipLaunchKernelGGL(k_gather<1>, grid, block, 0, (hipStream_t)stream, N, num_samples, D, x, ancestors, out);
+  return bjx_check_launch("bjx_smc_gather");
+}
+
+int bjx_smc_temper(void* stream, int64_t N, int64_t D, const float* lam, const float* logprior,
+                   const float* logprior_grad, const float* loglik, const float* loglik_grad, float* logp_out,
+                   float* grad_out) {
+  BJX_CHECK_ARG(N >= 0 && D > 0, "bjx_smc_temper: bad sizes");
+  if (N == 0) return 0;
+  BJX_CHECK_ARG(lam && logprior && logprior_grad && loglik && loglik_grad && logp_out && grad_out,
+                "bjx_smc_temper: null pointer");
+  const dim3 block(kBlock);
+  if (bjx_vec4_ok(D, logprior_grad, loglik_grad, grad_out))
+    hipLaunchKernelGGL(k_temper<4>, dim3(flat_grid(N * D / 4)), block, 0, (hipStream_t)stream, N, D, lam, logprior,
+                       logprior_grad, loglik, loglik_grad, logp_out, grad_out);
+  else
+    hipLaunchKernelGGL(k_temper<1>, dim3(flat_grid(N * D)), block, 0, (hipStream_t)stream, N, D, lam, logprior,
+                       logprior_grad, loglik, loglik_grad, logp_out, grad_out);
+  return bjx_check_launch("bjx_smc_temper");
+}
+
+int bjx_smc_reweight(void* stream, int64_t N, const float* loglik, const float* lam_old, const float* lam_new,
+                     float* weights_out, float* log_likelihood_increment_out, float* lam_out) {
+  BJX_CHECK_ARG(N >= 1, "bjx_smc_reweight: bad sizes");
+  BJX_CHECK_ARG(loglik && lam_old && lam_new && weights_out && log_likelihood_increment_out && lam_out,
+                "bjx_smc_reweight: null pointer");
+  hipLaunchKernelGGL(k_reweight, dim3(1), dim3(kRedBlock), 0, (hipStream_t)stream, N, loglik, lam_old, lam_new,
+                     weights_out, log_likelihood_increment_out, lam_out);
+  return bjx_check_launch("bjx_smc_reweight");
+}
+
+int bjx_smc_log_ess(void* stream, int64_t N, const float* log_weights, float* log_ess_out) {
+  BJX_CHECK_ARG(N >= 1, "bjx_smc_log_ess: bad sizes");
+  BJX_CHECK_ARG(log_weights && log_ess_out, "bjx_smc_log_ess: null pointer");
+  hipLaunchKernelGGL(k_log_ess, dim3(1), dim3(kRedBlock), 0, (hipStream_t)stream, N, log_weights, log_ess_out);
+  return bjx_check_launch("bjx_smc_log_ess");
+}
+
+int bjx_smc_ess_solve(void* stream, int64_t N, const float* loglik, float target_ess, const float* max_delta,
+                      const float* lam_old, float* delta_out, float* lam_new_out) {
+  BJX_CHECK_ARG(N >= 1 && target_ess > 0.0f && target_ess <= 1.0f, "bjx_smc_ess_solve: bad sizes");
+  BJX_CHECK_ARG(loglik && (max_delta || lam_old) && delta_out, "bjx_smc_ess_solve: null pointer");
+  const double log_target = log((double)N * (double)target_ess);
+  hipLaunchKernelGGL(k_ess_solve, dim3(1), dim3(kRedBlock), 0, (hipStream_t)stream, N, loglik, log_target,
+                     max_delta, lam_old, delta_out, lam_new_out);
+  return bjx_check_launch("bjx_smc_ess_solve");
+}
+
+}  // extern "C"

@@ -545,6 +545,55 @@ int bjx_ess_shrink(void* stream, uint32_t key0, uint32_t key1, int64_t chain_off
                    uint8_t* done, float* q_prop, float* logdensity_out, float* theta_out, int32_t* subiter_out,
                    float* momentum_out, int32_t* n_live);
 
+/* ---- SMC (blackjax.tempered_smc / adaptive_tempered_smc; blackjax/smc/) -----------------------
+ * One step = bjx_smc_resample -> bjx_smc_gather -> num_mcmc_steps transitions of an MCMC kernel on the tempered
+ * log-density (bjx_smc_temper after the two user callables) -> user log-likelihood -> bjx_smc_reweight; the adaptive
+ * sampler first runs bjx_smc_ess_solve.  Temperatures travel as device scalars: no entry point reads anything back.
+ *
+ * Resampling.  Cumulative weights in 2^-62 fixed point: wf_j = (int64) floor((double) w_j * 2^62) (w_j clamped to
+ * [0, 1], NaN = 0), C = inclusive prefix sum (integer, so independent of the tiling: tiles of bjx_smc_scan_tile()
+ * items, launch-separated -- tile sums, scan of the tile sums, apply; no workgroup waits on another).
+ *   pos_i = ((float) i + u_i) / (float) num_samples                       (fp32)
+ *   u_i = uniform(key, ()) [systematic] or uniform(key, (num_samples,))[i] [stratified != 0]
+ *   ancestors_out[i] = min(N - 1, #{j : C_j < (int64)((double) pos_i * 2^62)})
+ * 1 <= N <= 2^24, num_samples <= 2^24 (positions are fp32).  workspace: bjx_smc_resample_workspace_bytes(N) bytes
+ * (0 for an N out of range), 8-byte aligned.
+ * Replaces: smc/resampling.py::systematic, stratified (searchsorted on cumsum + clip). */
+int bjx_smc_scan_tile(void);
+int64_t bjx_smc_resample_workspace_bytes(int64_t N);
+int bjx_smc_resample(void* stream, uint32_t key0, uint32_t key1, int32_t stratified, int64_t N,
+                     int64_t num_samples, const float* weights, int64_t* workspace, int32_t* ancestors_out);
+/* out[i, :] = x[ancestors[i], :], x (N, D), out (num_samples, D), out of place; 16-byte accesses when D % 4 == 0 and
+ * both arrays are 16-byte aligned.  An index outside [0, N) is clamped into it.
+ * Replaces: smc/base.py::step (the tree_map of particles[resampling_idx]). */
+int bjx_smc_gather(void* stream, int64_t N, int64_t num_samples, int64_t D, const float* x,
+                   const int32_t* ancestors, float* out);
+/* Tempered log-posterior and gradient from the two callables' outputs, lam read from device memory:
+ *   logp_out = logprior + lam * loglik ; grad_out = logprior_grad + lam * loglik_grad
+ * product rounded, then sum rounded (no fused multiply-add).
+ * Replaces: smc/tempered.py::build_kernel (tempered_logposterior_fn) under jax.value_and_grad. */
+int bjx_smc_temper(void* stream, int64_t N, int64_t D, const float* lam, const float* logprior,
+                   const float* logprior_grad, const float* loglik, const float* loglik_grad, float* logp_out,
+                   float* grad_out);
+/* lw = (*lam_new - *lam_old) * loglik (0 when the difference is 0, whatever loglik is); a NaN or -inf lw is a
+ * particle of weight 0.  lse = logsumexp(lw) (fp64) ; weights_out = exp(lw - lse) ;
+ * *log_likelihood_increment_out = lse - log N ; *lam_out = *lam_new.  No particle of positive weight: weights NaN,
+ * increment -inf.  One workgroup.
+ * Replaces: smc/tempered.py::build_kernel (log_weights_fn) ; smc/base.py::step (normalisation, increment). */
+int bjx_smc_reweight(void* stream, int64_t N, const float* loglik, const float* lam_old, const float* lam_new,
+                     float* weights_out, float* log_likelihood_increment_out, float* lam_out);
+/* *log_ess_out = 2 logsumexp(lw) - logsumexp(2 lw), fp64 sums.  Replaces: smc/ess.py::log_ess. */
+int bjx_smc_log_ess(void* stream, int64_t N, const float* log_weights, float* log_ess_out);
+/* Largest temperature increment that keeps the ESS at the target, f(d) = log_ess(d * loglik) - log(N target_ess):
+ *   max = *max_delta, or 1 - *lam_old when max_delta is null
+ *   f(max) >= 0: delta = max ; else 30 halvings of [0, max] in fp32, left end moved to mid when f(mid) >= 0, delta =
+ *   the left end (the ESS at delta is never below the target).
+ * *lam_new_out (optional) = *lam_old + delta, exactly 1.0f when delta = 1 - *lam_old was taken whole.  The whole solve
+ * is one launch of one workgroup.
+ * Replaces: smc/ess.py::ess_solver ; smc/solver.py::dichotomy ; smc/adaptive_tempered.py::build_kernel (compute_delta). */
+int bjx_smc_ess_solve(void* stream, int64_t N, const float* loglik, float target_ess, const float* max_delta,
+                      const float* lam_old, float* delta_out, float* lam_new_out);
+
 /* Built-in synthetic targets (value + gradient in one pass, fp64-accumulated logp) used
  * as the "user callable" by the bench and parity tests.
  *   diag gaussian:  g = -(q*inv_var) ; logp = 0.5 * sum q*g     (tests/fixtures.py:60-78)
