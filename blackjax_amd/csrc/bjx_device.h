@@ -244,6 +244,24 @@ template <bool NT> __device__ __forceinline__ void st4_t(float* p, F4 v) {
   else st4(p, v);
 }
 
+// Write-through form (buffer_store_dwordx4 ... sc1): the bytes leave the XCD's L2 at once and no line is kept, where a
+// plain or nontemporal store keeps the line, dirty, for the end of the launch to write back.  For the cache-resident
+// HMC loop (flat leapfrog <-> gradient callable over one Infinity-Cache-sized block): the counters show that no read of
+// the next launch hits L2 whatever the stores do (profiles/l2_policy), so a kept line buys nothing and its write-back is
+// serial time at each of the loop's dependent boundaries.  Measured on 16 384 x 1 024 pseudo-random rows
+// (tools/lf_variants 1 policy): 64.63 -> 62.27 us per step with p, q and g written through.  For a thread's LAST
+// store only: a wave that goes on to further rows waits longer for a write-through store (the momentum draw with the
+// opening kick: 85 -> 97 us).
+// The store goes through a buffer descriptor of `bytes` bytes at `span`, both wave-uniform AND provably so (kernel
+// arguments, blockIdx) -- otherwise the compiler wraps the store in a readfirstlane loop.  The kernels describe only
+// the span their workgroup owns, so the 32-bit range and offset always fit; `off` is the lane's byte offset in it.
+__device__ __forceinline__ void st4_wt(float* span, int bytes, int off, F4 v) {
+  typedef unsigned bjx_u4v __attribute__((ext_vector_type(4)));
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(span, 0, bytes, 0x00020000);
+  const bjx_u4v t = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+  __builtin_amdgcn_raw_buffer_store_b128(t, rs, off, 0, /*aux: sc1*/ 16);
+}
+
 // One wavefront sweeps a row of D floats (D % 4 == 0) 16 bytes per lane: for every span of
 // U x 1 KB, `load(u, j)` is called for all its 16-byte pieces first and `body(u, j)` afterwards,
 // both in ascending j (so fp64 accumulations keep their order).  Written this way because a loop

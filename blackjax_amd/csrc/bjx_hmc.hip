@@ -319,8 +319,8 @@ k_leapfrog_diag(int64_t N, int64_t D, float eps_s, const float* __restrict__ eps
 // The leapfrog needs no row reduction, and many short waves fill the chip more evenly than one
 // wave per row (measured on pseudo-random data, tools/lf_variants: 46.6 vs 48.3 us for 16 384 rows
 // of 1 024, 233 vs 241 us for 65 536).  Workgroups are numbered from the END of the arrays for the
-// same Infinity-Cache reason as above.
-template <int KICKS, bool NT = false>
+// same Infinity-Cache reason as above.  WT (cache-resident launches): p and q are written through L2 (st4_wt).
+template <int KICKS, bool NT = false, bool WT = false>
 __global__ void __launch_bounds__(kBlock)
 k_leapfrog_diag_flat(int64_t D, int bpr, float eps_s, const float* __restrict__ eps_pc,
                      const float* __restrict__ imm, int64_t imm_stride, const float* q_in,
@@ -329,7 +329,7 @@ k_leapfrog_diag_flat(int64_t D, int bpr, float eps_s, const float* __restrict__ 
                      float drift) {
   const unsigned b = BJX_REVERSE_ROWS ? gridDim.x - 1 - blockIdx.x : blockIdx.x;
   const int64_t r = b / (unsigned)bpr;
-  const int64_t j = (int64_t)(b - (unsigned)r * (unsigned)bpr) * 1024 + threadIdx.x * 4;
+  const int64_t j0 = (int64_t)(b - (unsigned)r * (unsigned)bpr) * 1024, j = j0 + threadIdx.x * 4;
   const int64_t at = r * D + j;
   if (n_steps && step_idx >= n_steps[r]) {
     if (q_out != q_in) {
@@ -353,8 +353,13 @@ k_leapfrog_diag_flat(int64_t D, int bpr, float eps_s, const float* __restrict__ 
   }
   qn.x = fmaf(ed, mm.x * pn.x, qq.x); qn.y = fmaf(ed, mm.y * pn.y, qq.y);
   qn.z = fmaf(ed, mm.z * pn.z, qq.z); qn.w = fmaf(ed, mm.w * pn.w, qq.w);
-  st4_t<NT>(p_out + at, pn);
-  st4_t<NT>(q_out + at, qn);
+  if constexpr (WT) {  // the workgroup's 4 KB span of each array
+    st4_wt(p_out + (r * D + j0), 4096, threadIdx.x * 16, pn);
+    st4_wt(q_out + (r * D + j0), 4096, threadIdx.x * 16, qn);
+  } else {
+    st4_t<NT>(p_out + at, pn);
+    st4_t<NT>(q_out + at, qn);
+  }
 }
 
 // The same one-piece-per-lane stage for ANY row length that is a multiple of 4 floats: lane i of
@@ -362,7 +367,7 @@ k_leapfrog_diag_flat(int64_t D, int bpr, float eps_s, const float* __restrict__ 
 // wave a row of D = 64 floats keeps 16 of 64 lanes busy (measured: 49 % of the HBM peak at
 // 524 288 x 64, 84 % at D = 100); here every lane works whatever D is.  32-bit index arithmetic
 // (the host checks N * D / 4 < 2^31).
-template <int KICKS>
+template <int KICKS, bool WT = false>
 __global__ void __launch_bounds__(kBlock)
 k_leapfrog_diag_flat_any(uint32_t total4, uint32_t D4, float eps_s, const float* __restrict__ eps_pc,
                          const float* __restrict__ imm, uint32_t imm_stride4, const float* q_in,
@@ -395,8 +400,16 @@ k_leapfrog_diag_flat_any(uint32_t total4, uint32_t D4, float eps_s, const float*
   }
   qn.x = fmaf(ed, mm.x * pn.x, qq.x); qn.y = fmaf(ed, mm.y * pn.y, qq.y);
   qn.z = fmaf(ed, mm.z * pn.z, qq.z); qn.w = fmaf(ed, mm.w * pn.w, qq.w);
-  st4(p_out + at, pn);
-  st4(q_out + at, qn);
+  if constexpr (WT) {
+    // the workgroup's span of at most 4 KB: the last one may be ragged, and its descriptor ends with the arrays
+    const uint32_t left = total4 - b * kBlock;
+    const int span_bytes = (int)(left < (uint32_t)kBlock ? left : (uint32_t)kBlock) * 16;
+    st4_wt(p_out + (int64_t)b * kBlock * 4, span_bytes, threadIdx.x * 16, pn);
+    st4_wt(q_out + (int64_t)b * kBlock * 4, span_bytes, threadIdx.x * 16, qn);
+  } else {
+    st4(p_out + at, pn);
+    st4(q_out + at, qn);
+  }
 }
 
 // ------------------------------------------------------------------------------ finish
@@ -851,6 +864,7 @@ int bjx_leapfrog_diag_coef(void* stream, int64_t N, int64_t D, int n_kicks, floa
     const char* e = getenv("BJX_LF_FLAT");
     return e ? atoi(e) != 0 : true;
   }();
+  const bool wt = bjx_lf_write_through();
   if (flat_ok && D % 1024 == 0 && N * (D / 1024) < ((int64_t)1 << 31) &&
       bjx_vec4_ok(D, imm, q_in, p_in, g, q_out, p_out)) {
     const int bpr = (int)(D / 1024);
@@ -861,11 +875,17 @@ int bjx_leapfrog_diag_coef(void* stream, int64_t N, int64_t D, int n_kicks, floa
     static const int nt_mode = [] { const char* e = getenv("BJX_LF_NT"); return e ? atoi(e) : -1; }();
     const int64_t launch_bytes = N * D * 4 * (3 + (imm_stride ? 1 : 0));
     const bool nt = nt_mode < 0 ? launch_bytes > ((int64_t)256 << 20) : nt_mode != 0;
-#define BJX_LFF(K, T)                                                                                    \
-  hipLaunchKernelGGL((k_leapfrog_diag_flat<K, T>), fgrid, block, 0, s, D, bpr, eps, eps_per_chain, imm, \
+    // a launch that stays cache-resident writes p and q through L2 (st4_wt; BJX_LF_POLICY=0: plain stores)
+#define BJX_LFF(K, T, W)                                                                                    \
+  hipLaunchKernelGGL((k_leapfrog_diag_flat<K, T, W>), fgrid, block, 0, s, D, bpr, eps, eps_per_chain, imm, \
                      imm_stride, q_in, p_in, g, q_out, p_out, n_steps, step_idx, kick_a, kick_b, drift)
-    if (n_kicks == 1) { if (nt) BJX_LFF(1, true); else BJX_LFF(1, false); }
-    else { if (nt) BJX_LFF(2, true); else BJX_LFF(2, false); }
+#define BJX_LFF_K(K)                     \
+  if (nt) BJX_LFF(K, true, false);       \
+  else if (wt) BJX_LFF(K, false, true);  \
+  else BJX_LFF(K, false, false)
+    if (n_kicks == 1) { BJX_LFF_K(1); }
+    else { BJX_LFF_K(2); }
+#undef BJX_LFF_K
 #undef BJX_LFF
   } else if (flat_ok && (D / 4) % 64 != 0 && N * (D / 4) < ((int64_t)1 << 31) &&
              bjx_vec4_ok(D, imm, q_in, p_in, g, q_out, p_out)) {
@@ -873,12 +893,12 @@ int bjx_leapfrog_diag_coef(void* stream, int64_t N, int64_t D, int n_kicks, floa
     const uint32_t D4 = (uint32_t)(D / 4), total4 = (uint32_t)(N * (D / 4));
     const dim3 fgrid((total4 + kBlock - 1) / kBlock);
     const uint32_t is4 = imm_stride ? D4 : 0u;
-    if (n_kicks == 1)
-      hipLaunchKernelGGL(k_leapfrog_diag_flat_any<1>, fgrid, block, 0, s, total4, D4, eps, eps_per_chain,
-                         imm, is4, q_in, p_in, g, q_out, p_out, n_steps, step_idx, kick_a, kick_b, drift);
-    else
-      hipLaunchKernelGGL(k_leapfrog_diag_flat_any<2>, fgrid, block, 0, s, total4, D4, eps, eps_per_chain,
-                         imm, is4, q_in, p_in, g, q_out, p_out, n_steps, step_idx, kick_a, kick_b, drift);
+#define BJX_LFA(K, W)                                                                                       \
+  hipLaunchKernelGGL((k_leapfrog_diag_flat_any<K, W>), fgrid, block, 0, s, total4, D4, eps, eps_per_chain, imm, \
+                     is4, q_in, p_in, g, q_out, p_out, n_steps, step_idx, kick_a, kick_b, drift)
+    if (n_kicks == 1) { if (wt) BJX_LFA(1, true); else BJX_LFA(1, false); }
+    else { if (wt) BJX_LFA(2, true); else BJX_LFA(2, false); }
+#undef BJX_LFA
   } else if (bjx_vec4_ok(D, imm, q_in, p_in, g, q_out, p_out)) {
     if (n_kicks == 1) BJX_LF(4, 1); else BJX_LF(4, 2);
   } else {

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 // thread-local last-error message (defined in bjx_api.hip)
 void bjx_set_error(const char* fmt, ...);
@@ -33,4 +34,15 @@ static inline bool bjx_vec4_ptr_ok(const void* p) { return p == nullptr || ((uin
 template <typename... P>
 static inline bool bjx_vec4_ok(int64_t D, P... ptrs) {
   return (D % 4 == 0) && (bjx_vec4_ptr_ok((const void*)ptrs) && ...);
+}
+
+// Store policy of the cache-resident HMC loop kernels (flat leapfrog, gradient-only Gaussian callable): p, q and g
+// written through L2 (st4_wt, bjx_device.h).  BJX_LF_POLICY=0 gives plain stores (A/B: tools/README.md); read
+// once per process.
+static inline bool bjx_lf_write_through() {
+  static const bool on = [] {
+    const char* e = getenv("BJX_LF_POLICY");
+    return e ? atoi(e) != 0 : true;
+  }();
+  return on;
 }

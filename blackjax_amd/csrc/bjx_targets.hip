@@ -91,31 +91,41 @@ __device__ __forceinline__ unsigned grad_span_of_workgroup() {
 // fp64 row sum nothing is per row, so the launch takes the leapfrog's geometry (k_leapfrog_diag_flat): one 16-byte
 // piece per lane, one workgroup per 4 KB span of a row (D % 1024 == 0), no loop.  Workgroups ASCEND (first row
 // first, grad_span_of_workgroup): the leapfrog that follows sweeps last-to-first and finds the rows written last
-// still in cache.
-template <bool NT = false>
+// still in cache.  WT (cache-resident launches): g is written through L2 (st4_wt).
+template <bool NT = false, bool WT = false>
 __global__ void __launch_bounds__(kBlock)
 k_diag_gaussian_grad_flat(int64_t D, int bpr, const float* __restrict__ iv, const float* __restrict__ q,
                           float* __restrict__ g) {
   const unsigned b = grad_span_of_workgroup();
   const int64_t r = b / (unsigned)bpr;
-  const int64_t j = (int64_t)(b - (unsigned)r * (unsigned)bpr) * 1024 + threadIdx.x * 4;
+  const int64_t j0 = (int64_t)(b - (unsigned)r * (unsigned)bpr) * 1024, j = j0 + threadIdx.x * 4;
   const int64_t at = r * D + j;
   const F4 qq = ld4_t<NT>(q + at), vv = ld4(iv + j);
-  st4_t<NT>(g + at, F4{-(qq.x * vv.x), -(qq.y * vv.y), -(qq.z * vv.z), -(qq.w * vv.w)});
+  const F4 gg{-(qq.x * vv.x), -(qq.y * vv.y), -(qq.z * vv.z), -(qq.w * vv.w)};
+  if constexpr (WT) st4_wt(g + (r * D + j0), 4096, threadIdx.x * 16, gg);  // the workgroup's 4 KB span
+  else st4_t<NT>(g + at, gg);
 }
 
 // any row length that is a multiple of 4 floats: lane i owns the i-th 16-byte piece of the (N, D) arrays
 // (k_leapfrog_diag_flat_any's indexing; the host checks N * D / 4 < 2^31)
-template <bool NT = false>
+template <bool NT = false, bool WT = false>
 __global__ void __launch_bounds__(kBlock)
 k_diag_gaussian_grad_flat_any(uint32_t total4, uint32_t D4, const float* __restrict__ iv,
                               const float* __restrict__ q, float* __restrict__ g) {
-  const uint32_t i = grad_span_of_workgroup() * kBlock + threadIdx.x;
+  const uint32_t b = grad_span_of_workgroup();
+  const uint32_t i = b * kBlock + threadIdx.x;
   if (i >= total4) return;
   const uint32_t j4 = i % D4;
   const int64_t at = (int64_t)i * 4;
   const F4 qq = ld4_t<NT>(q + at), vv = ld4(iv + (int64_t)j4 * 4);
-  st4_t<NT>(g + at, F4{-(qq.x * vv.x), -(qq.y * vv.y), -(qq.z * vv.z), -(qq.w * vv.w)});
+  const F4 gg{-(qq.x * vv.x), -(qq.y * vv.y), -(qq.z * vv.z), -(qq.w * vv.w)};
+  if constexpr (WT) {
+    // the workgroup's span of at most 4 KB: the last one may be ragged, and its descriptor ends with the array
+    const uint32_t left = total4 - b * kBlock;
+    st4_wt(g + (int64_t)b * kBlock * 4, (int)(left < (uint32_t)kBlock ? left : (uint32_t)kBlock) * 16, threadIdx.x * 16, gg);
+  } else {
+    st4_t<NT>(g + at, gg);
+  }
 }
 
 // rows that are not a multiple of 4 floats (or unaligned buffers): one row per wave, 4 bytes per lane
@@ -286,15 +296,20 @@ int bjx_target_diag_gaussian_grad(void* stream, int64_t N, int64_t D, const floa
   static const int nt_mode = [] { const char* e = getenv("BJX_LF_NT"); return e ? atoi(e) : -1; }();
   const bool nt = nt_mode < 0 ? N * D * 8 > ((int64_t)256 << 20) : nt_mode != 0;
   const bool v4 = bjx_vec4_ok(D, inv_var, q, g_out);
+  // a launch that stays cache-resident writes g through L2 (st4_wt; BJX_LF_POLICY=0: plain stores)
+  const bool wt = bjx_lf_write_through();
   if (v4 && D % 1024 == 0 && N * (D / 1024) < ((int64_t)1 << 31)) {
     const int bpr = (int)(D / 1024);
     const dim3 grid((unsigned)(N * bpr));
     if (nt) hipLaunchKernelGGL(k_diag_gaussian_grad_flat<true>, grid, block, 0, s, D, bpr, inv_var, q, g_out);
+    else if (wt) hipLaunchKernelGGL((k_diag_gaussian_grad_flat<false, true>), grid, block, 0, s, D, bpr, inv_var, q, g_out);
     else hipLaunchKernelGGL(k_diag_gaussian_grad_flat<false>, grid, block, 0, s, D, bpr, inv_var, q, g_out);
   } else if (v4 && N * (D / 4) < ((int64_t)1 << 31)) {
     const uint32_t D4 = (uint32_t)(D / 4), total4 = (uint32_t)(N * (D / 4));
     const dim3 grid((total4 + kBlock - 1) / kBlock);
     if (nt) hipLaunchKernelGGL(k_diag_gaussian_grad_flat_any<true>, grid, block, 0, s, total4, D4, inv_var, q, g_out);
+    else if (wt)
+      hipLaunchKernelGGL((k_diag_gaussian_grad_flat_any<false, true>), grid, block, 0, s, total4, D4, inv_var, q, g_out);
     else hipLaunchKernelGGL(k_diag_gaussian_grad_flat_any<false>, grid, block, 0, s, total4, D4, inv_var, q, g_out);
   } else {
     hipLaunchKernelGGL(k_diag_gaussian_grad_rows, dim3(bjx_row_grid(N, kWavesPerBlock)), block, 0, s, N, D,

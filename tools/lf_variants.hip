@@ -2,9 +2,14 @@
 // headline shape (rows of 1 024 floats), to see how far the product kernels are from what the
 // memory system gives a plain flat sweep of the same bytes.
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/lf_variants.hip -o tools/lf_variants
+//   tools/lf_variants 1          launch-geometry table and the callable's forms (pseudo-random data)
+//   tools/lf_variants 1 policy   per-array cache policy of the product-shaped loop (profiles/l2_policy)
+//   tools/lf_variants 1 policy e one row of that table at 16 384 rows, three loops, for a counter run
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 struct alignas(16) F4 { float x, y, z, w; };
 #define D4 256  // float4 per row (D = 1024)
 
@@ -129,6 +134,52 @@ __global__ void __launch_bounds__(256) call_piece_grad(const F4* __restrict__ q,
   g[i] = F4{-(a.x * v.x), -(a.y * v.y), -(a.z * v.z), -(a.w * v.w)};
 }
 
+// ---- per-array cache policy of the product-shaped loop (lf_piece_rev ; call_piece_grad<true>): each of the three
+// stored arrays (p, q in the leapfrog, g in the callable) takes a store flavour, the leapfrog's load of p a load flavour.
+// PLAIN and NTP keep the line in the XCD's L2; SC1 writes through and drops it (buffer store with aux = 16; the
+// descriptor covers the workgroup's own 4 KB span, so it is built from workgroup-uniform values only).
+enum { PLAIN = 0, NTP = 1, SC1 = 2 };
+typedef float f4v __attribute__((ext_vector_type(4)));
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
+template <int POL> __device__ __forceinline__ void st_pol(F4* span, F4 v) {
+  if constexpr (POL == SC1) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(span, 0, 4096, 0x00020000);
+    const u4v t = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+    __builtin_amdgcn_raw_buffer_store_b128(t, rs, (int)(threadIdx.x * 16), 0, 16);
+  } else if constexpr (POL == NTP) {
+    const f4v t = {v.x, v.y, v.z, v.w};
+    __builtin_nontemporal_store(t, reinterpret_cast<f4v*>(span + threadIdx.x));
+  } else {
+    span[threadIdx.x] = v;
+  }
+}
+template <int SP, int SQ, int LP>
+__global__ void __launch_bounds__(256) lf_piece_rev_pol(F4* q, F4* p, const F4* __restrict__ g,
+                                                        const F4* __restrict__ imm, float h, float ed) {
+  const size_t s = (size_t)(gridDim.x - 1 - blockIdx.x) * 256, i = s + threadIdx.x;
+  F4 pp;
+  if constexpr (LP == NTP) { const f4v t = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p + i)); pp = F4{t.x, t.y, t.z, t.w}; }
+  else pp = p[i];
+  F4 gg = g[i], qq = q[i];
+  const F4 mm = imm[threadIdx.x];
+  lf_math(pp, gg, qq, mm, h, ed);
+  st_pol<SP>(p + s, pp); st_pol<SQ>(q + s, qq);
+}
+template <int SG>
+__global__ void __launch_bounds__(256) call_piece_grad_pol(const F4* __restrict__ q, F4* __restrict__ g,
+                                                           const F4* __restrict__ iv) {
+  const size_t s = (size_t)(blockIdx.x ^ 7u) * 256;
+  const F4 a = q[s + threadIdx.x], v = iv[threadIdx.x];
+  st_pol<SG>(g + s, F4{-(a.x * v.x), -(a.y * v.y), -(a.z * v.z), -(a.w * v.w)});
+}
+// order-independent sum of the bit patterns: every policy must leave the bits the plain stores leave
+__global__ void bits_sum(const unsigned* a, size_t n, unsigned long long* out) {
+  unsigned long long s = 0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    s += (unsigned long long)a[i] * (unsigned long long)((i & 1023) + 1);
+  atomicAdd(out, s);
+}
+
 // pseudo-random fill: all-zero buffers toggle no data lines and flatter a power-limited part
 __global__ void fill_random(float* a, size_t n, unsigned seed, float lo, float hi) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -138,9 +189,128 @@ __global__ void fill_random(float* a, size_t n, unsigned seed, float lo, float h
   }
 }
 
+typedef void (*lf_fn)(F4*, F4*, const F4*, const F4*, float, float);
+typedef void (*gr_fn)(const F4*, F4*, const F4*);
+static const char* kPolName[3] = {"plain", "nt", "sc1"};
+static double median_of(const float* v, int n) {
+  float t[16]; std::copy(v, v + n, t); std::sort(t, t + n); return t[n / 2];
+}
+
+// per-array policy table: rows interleaved inside each of five repeats, one process
+static int policy_main(const char* only) {
+  const int L = 50, REPS = 5, LOOPS = 6;
+  struct Desc { const char* name; int sp, sq, sg, lp; lf_fn lf; gr_fn gr; };
+  const Desc rows[] = {
+      {"parent", PLAIN, PLAIN, PLAIN, PLAIN, lf_piece_rev_pol<PLAIN, PLAIN, PLAIN>, call_piece_grad_pol<PLAIN>},
+      {"a", SC1, PLAIN, PLAIN, PLAIN, lf_piece_rev_pol<SC1, PLAIN, PLAIN>, call_piece_grad_pol<PLAIN>},
+      {"b", SC1, PLAIN, PLAIN, NTP, lf_piece_rev_pol<SC1, PLAIN, NTP>, call_piece_grad_pol<PLAIN>},
+      {"c", SC1, NTP, PLAIN, PLAIN, lf_piece_rev_pol<SC1, NTP, PLAIN>, call_piece_grad_pol<PLAIN>},
+      {"d", SC1, SC1, PLAIN, PLAIN, lf_piece_rev_pol<SC1, SC1, PLAIN>, call_piece_grad_pol<PLAIN>},
+      {"e", SC1, PLAIN, SC1, PLAIN, lf_piece_rev_pol<SC1, PLAIN, PLAIN>, call_piece_grad_pol<SC1>},
+      {"f", SC1, SC1, SC1, PLAIN, lf_piece_rev_pol<SC1, SC1, PLAIN>, call_piece_grad_pol<SC1>},
+      {"g", SC1, NTP, NTP, PLAIN, lf_piece_rev_pol<SC1, NTP, PLAIN>, call_piece_grad_pol<NTP>},
+      {"h", NTP, PLAIN, PLAIN, PLAIN, lf_piece_rev_pol<NTP, PLAIN, PLAIN>, call_piece_grad_pol<PLAIN>},
+      {"i", NTP, PLAIN, PLAIN, NTP, lf_piece_rev_pol<NTP, PLAIN, NTP>, call_piece_grad_pol<PLAIN>},
+  };
+  const int R = (int)(sizeof(rows) / sizeof(rows[0]));
+  F4 *q, *p, *g, *imm, *iv;
+  unsigned long long* sum;
+  const size_t maxN = 65536;
+  hipMalloc(&q, maxN * D4 * 16); hipMalloc(&p, maxN * D4 * 16); hipMalloc(&g, maxN * D4 * 16);
+  hipMalloc(&imm, D4 * 16); hipMalloc(&iv, D4 * 16); hipMalloc(&sum, 3 * 8);
+  fill_random<<<4, 256>>>((float*)imm, 1024, 4u, 0.5f, 2.0f);
+  fill_random<<<4, 256>>>((float*)iv, 1024, 6u, 0.5f, 2.0f);
+  hipEvent_t e0, e1, e2; hipEventCreate(&e0); hipEventCreate(&e1); hipEventCreate(&e2);
+  const float h = 0.125f, ed = 0.25f;  // eps^2 * imm * inv_var <= 0.25: the loop's orbit stays bounded
+  auto refill = [&](size_t N) {
+    fill_random<<<4096, 256>>>((float*)q, N * 1024, 1u, -1.0f, 1.0f);
+    fill_random<<<4096, 256>>>((float*)p, N * 1024, 2u, -1.0f, 1.0f);
+    fill_random<<<4096, 256>>>((float*)g, N * 1024, 3u, -1.0f, 1.0f);
+  };
+  if (only) {
+    const size_t N = 16384;
+    const unsigned pieces = (unsigned)(N * D4 / 256);
+    for (int r = 0; r < R; ++r) {
+      if (strcmp(rows[r].name, only)) continue;
+      refill(N);
+      for (int s = 0; s < 3 * L; ++s) { rows[r].lf<<<pieces, 256>>>(q, p, g, imm, h, ed); rows[r].gr<<<pieces, 256>>>(q, g, iv); }
+      hipDeviceSynchronize();
+      printf("row %s: %d steps at %zu rows\n", only, 3 * L, N);
+      return 0;
+    }
+    fprintf(stderr, "no such row: %s\n", only);
+    return 2;
+  }
+  printf("data: pseudo-random; loop = lf_piece_rev ; call_piece_grad<XCD>, %d steps per loop, %d timed loops per repeat, "
+         "%d repeats (rows interleaved inside each repeat)\n", L, LOOPS, REPS);
+  int bad = 0;
+  for (size_t N : {(size_t)16384, (size_t)65536}) {
+    const unsigned pieces = (unsigned)(N * D4 / 256);
+    // every policy leaves the parent's bits (one loop from the same start)
+    unsigned long long ref[3] = {0, 0, 0};
+    for (int r = 0; r < R; ++r) {
+      refill(N);
+      for (int s = 0; s < L; ++s) { rows[r].lf<<<pieces, 256>>>(q, p, g, imm, h, ed); rows[r].gr<<<pieces, 256>>>(q, g, iv); }
+      hipMemset(sum, 0, 24);
+      bits_sum<<<2048, 256>>>((const unsigned*)q, N * 1024, sum);
+      bits_sum<<<2048, 256>>>((const unsigned*)p, N * 1024, sum + 1);
+      bits_sum<<<2048, 256>>>((const unsigned*)g, N * 1024, sum + 2);
+      unsigned long long hs[3];
+      hipMemcpy(hs, sum, 24, hipMemcpyDeviceToHost);
+      if (r == 0) std::copy(hs, hs + 3, ref);
+      const bool same = hs[0] == ref[0] && hs[1] == ref[1] && hs[2] == ref[2];
+      if (!same) { ++bad; printf("N %6zu row %-6s : BITS DIFFER from parent\n", N, rows[r].name); }
+    }
+    printf("N %6zu : q, p, g after one loop %s\n", N, bad ? "DIFFER" : "bit-identical to the parent in every row");
+    static float loop[16][REPS], lfa[16][REPS], gra[16][REPS];
+    for (int rep = 0; rep < REPS; ++rep) {
+      for (int r = 0; r < R; ++r) {
+        auto lf = [&]() { rows[r].lf<<<pieces, 256>>>(q, p, g, imm, h, ed); };
+        auto gr = [&]() { rows[r].gr<<<pieces, 256>>>(q, g, iv); };
+        refill(N);
+        for (int s = 0; s < L; ++s) { lf(); gr(); }  // warm, untimed
+        refill(N);
+        hipEventRecord(e0);
+        for (int s = 0; s < LOOPS * L; ++s) { lf(); gr(); }
+        hipEventRecord(e1);
+        hipEventSynchronize(e1);
+        float ms; hipEventElapsedTime(&ms, e0, e1);
+        loop[r][rep] = ms * 1e3f / (LOOPS * L);
+        refill(N);
+        hipEventRecord(e0);
+        for (int s = 0; s < LOOPS * L; ++s) lf();
+        hipEventRecord(e1);
+        for (int s = 0; s < LOOPS * L; ++s) gr();
+        hipEventRecord(e2);
+        hipEventSynchronize(e2);
+        float a, b; hipEventElapsedTime(&a, e0, e1); hipEventElapsedTime(&b, e1, e2);
+        lfa[r][rep] = a * 1e3f / (LOOPS * L); gra[r][rep] = b * 1e3f / (LOOPS * L);
+      }
+    }
+    const double pmed = median_of(loop[0], REPS);
+    const double pspread = *std::max_element(loop[0], loop[0] + REPS) - *std::min_element(loop[0], loop[0] + REPS);
+    printf("N %6zu : parent loop median %.2f us/step, max - min %.2f ; candidate threshold: median < %.2f\n", N, pmed, pspread,
+           pmed - 3.0 * pspread);
+    for (int r = 0; r < R; ++r) {
+      const double med = median_of(loop[r], REPS);
+      printf("N %6zu row %-6s p-st %-5s q-st %-5s g-st %-5s p-ld %-5s | loop us/step", N, rows[r].name, kPolName[rows[r].sp],
+             kPolName[rows[r].sq], kPolName[rows[r].sg], kPolName[rows[r].lp]);
+      for (int k = 0; k < REPS; ++k) printf(" %6.2f", loop[r][k]);
+      printf(" median %6.2f | lf alone", med);
+      for (int k = 0; k < REPS; ++k) printf(" %6.2f", lfa[r][k]);
+      printf(" median %6.2f | grad alone", median_of(lfa[r], REPS));
+      for (int k = 0; k < REPS; ++k) printf(" %6.2f", gra[r][k]);
+      printf(" median %6.2f | %s\n", median_of(gra[r], REPS),
+             r == 0 ? "parent" : med < pmed - 3.0 * pspread ? "CANDIDATE" : "no candidate");
+    }
+  }
+  return bad ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
   const int L = 50;
   const bool randomize = argc > 1 && atoi(argv[1]) != 0;
+  if (argc > 2 && !strcmp(argv[2], "policy")) return policy_main(argc > 3 ? argv[3] : nullptr);
   F4 *q, *p, *g, *imm, *mu, *pr;
   const size_t maxN = 65536;
   hipMalloc(&q, maxN * D4 * 16); hipMalloc(&p, maxN * D4 * 16); hipMalloc(&g, maxN * D4 * 16);
