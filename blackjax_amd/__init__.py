@@ -14,9 +14,10 @@ from . import dynamic_hmc as _dynamic_hmc
 from . import elliptical_slice as _elliptical_slice
 from . import ghmc as _ghmc
 from . import hmc as _hmc
+from . import irmh as _irmh
 from . import mala as _mala
 from . import nuts as _nuts
-from . import adaptation, chees, diagnostics, distributed, integrators, meads, metrics, optim, random, rtc, smc, targets, util
+from . import adaptation, chees, diagnostics, distributed, integrators, meads, metrics, optim, random, random_walk, rtc, smc, targets, util
 from .adaptation import staged_adaptation, window_adaptation
 from .chees import chees_adaptation
 from .meads import meads_adaptation
@@ -74,10 +75,19 @@ barker_proposal = barker
 # Elliptical slice sampling (blackjax/mcmc/elliptical_slice.py): Gaussian prior, value-only log-likelihood, no gradient
 elliptical_slice = GenerateSamplingAPI(_elliptical_slice.as_top_level_api, _elliptical_slice.init,
                                        _elliptical_slice.build_kernel)
+# Random-walk Metropolis (blackjax/mcmc/random_walk.py, irmh.py): gradient-free, value-only log-density.  rmh takes any
+# batched proposal generator, additive_step_random_walk adds a random step (normal_random_walk: the fused Gaussian
+# step), irmh proposes independently of the position
+rmh = GenerateSamplingAPI(random_walk.rmh_as_top_level_api, random_walk.init, random_walk.build_rmh)
+additive_step_random_walk = GenerateSamplingAPI(random_walk.additive_step_random_walk, random_walk.init,
+                                                random_walk.build_additive_step)
+additive_step_random_walk.normal_random_walk = random_walk.normal_random_walk
+normal_random_walk = random_walk.normal_random_walk
+irmh = GenerateSamplingAPI(_irmh.as_top_level_api, _irmh.init, _irmh.build_kernel)
 # Tempered SMC (blackjax/smc/tempered.py, adaptive_tempered.py): the particles are the chain batch, the move is
 # num_mcmc_steps transitions of the samplers above, resampling / reweighting / the ESS solve are HIP kernels
 tempered_smc = GenerateSamplingAPI(smc.tempered.as_top_level_api, smc.tempered.init, smc.tempered.build_kernel)
 adaptive_tempered_smc = GenerateSamplingAPI(smc.adaptive_tempered.as_top_level_api, smc.adaptive_tempered.init,
                                             smc.adaptive_tempered.build_kernel)
 
-__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "barker", "barker_proposal", "elliptical_slice", "tempered_smc", "adaptive_tempered_smc", "smc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]
+__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "barker", "barker_proposal", "elliptical_slice", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "smc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]

@@ -306,9 +306,16 @@ SIGNATURES.update({
     "bjx_smc_resample": [c_void_p, c_uint32, c_uint32, ctypes.c_int32, c_int64, c_int64, _f32p, c_void_p, c_void_p],
     "bjx_smc_gather": [c_void_p, c_int64, c_int64, c_int64, _f32p, c_void_p, _f32p],
     "bjx_smc_temper": [c_void_p, c_int64, c_int64] + [_f32p] * 7,
+    "bjx_smc_temper_value": [c_void_p, c_int64] + [_f32p] * 4,
     "bjx_smc_reweight": [c_void_p, c_int64] + [_f32p] * 6,
     "bjx_smc_log_ess": [c_void_p, c_int64, _f32p, _f32p],
     "bjx_smc_ess_solve": [c_void_p, c_int64, _f32p, c_float, _f32p, _f32p, _f32p, _f32p],
+})
+# include/bjx_hip.h "random walk" (rmh / additive_step_random_walk / irmh: keyed noise, fused propose, accept + select)
+SIGNATURES.update({
+    "bjx_rw_noise": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, ctypes.c_int32, c_int64, c_int64, _f32p],
+    "bjx_rw_propose": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float] + [_f32p] * 4,
+    "bjx_rw_finish": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64] + [_f32p] * 9 + [_u8p],
 })
 INT64_FUNCTIONS = {"bjx_pool_workspace_bytes": [c_int64, c_int64],
                    "bjx_meads_workspace_bytes": [c_int64, c_int64],

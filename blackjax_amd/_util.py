@@ -392,6 +392,34 @@ def eval_logdensity(vg: Callable, q: torch.Tensor):
     return logp.contiguous(), g.contiguous()
 
 
+def eval_value(logdensity_fn: Callable, q: torch.Tensor) -> torch.Tensor:
+    """The log-density at ``q`` as contiguous fp32 ``(N,)``, paying for no gradient where the callable allows it
+    (the gradient-free samplers: ``random_walk``, ``irmh``).  In order:
+
+    1. an object offering ``_bjx_value(q)`` is asked for it (``smc.tempered.TemperedLogDensity``);
+    2. a ``_bjx_value_and_grad`` / ``_bjx_returns_pair`` callable computes the pair in its own way (one fused launch
+       for ``blackjax_amd.targets``): it is called as is and the gradient is dropped;
+    3. anything else is called on ``q.detach()`` under ``torch.no_grad()`` -- never traced, never differentiated; a
+       returned ``(logp, grad)`` pair gives its first element."""
+    f = getattr(logdensity_fn, "_bjx_value", None)
+    if f is not None:
+        out = f(q)
+    elif getattr(logdensity_fn, "_bjx_value_and_grad", False) or getattr(logdensity_fn, "_bjx_returns_pair", False):
+        out = logdensity_fn(q)[0]
+    else:
+        with torch.no_grad():
+            out = logdensity_fn(q.detach())
+        if isinstance(out, (tuple, list)):
+            out = out[0]
+    if out.shape != q.shape[:1]:
+        raise ValueError(f"logdensity_fn must return logp of shape {tuple(q.shape[:1])}, got {tuple(out.shape)}")
+    if out.device != q.device:
+        raise RuntimeError(f"logdensity_fn returned logp on {out.device} for positions on {q.device}")
+    if out.dtype != torch.float32:
+        out = out.float()
+    return out.detach().contiguous()
+
+
 def eval_into(vg: Callable, q: torch.Tensor, logp_out: torch.Tensor, g_out: torch.Tensor, need_logp: bool = True):
     """``eval_logdensity`` for a driver that owns the output buffers.  A callable may offer two optional capabilities
     (``blackjax_amd.targets`` do; a traced function does once its generated kernel exists):

@@ -165,6 +165,19 @@ k_temper(int64_t N, int64_t D, const float* __restrict__ lam_p, const float* __r
   }
 }
 
+// The value alone: lp + lam * ll, the product rounded before the sum exactly as k_temper forms lp_out, so a value-only
+// sampler (random walk) and a gradient sampler see the same tempered log-density bit for bit.
+__global__ void __launch_bounds__(kBlock)
+k_temper_value(int64_t N, const float* __restrict__ lam_p, const float* __restrict__ lp,
+               const float* __restrict__ ll, float* __restrict__ lp_out) {
+  const float lam = *lam_p;
+  const int64_t nthr = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += nthr) {
+    const float t = lam * ll[i];
+    lp_out[i] = lp[i] + t;
+  }
+}
+
 // ---- one-workgroup reductions over (N,) -------------------------------------------------------------------
 __device__ __forceinline__ double block_sum(double v, double* sh) {
   v = wave_sum(v);
@@ -390,6 +403,16 @@ int bjx_smc_temper(void* stream, int64_t N, int64_t D, const float* lam, const f
     hipLaunchKernelGGL(k_temper<1>, dim3(flat_grid(N * D)), block, 0, (hipStream_t)stream, N, D, lam, logprior,
                        logprior_grad, loglik, loglik_grad, logp_out, grad_out);
   return bjx_check_launch("bjx_smc_temper");
+}
+
+int bjx_smc_temper_value(void* stream, int64_t N, const float* lam, const float* logprior, const float* loglik,
+                         float* logp_out) {
+  BJX_CHECK_ARG(N >= 0, "bjx_smc_temper_value: bad sizes");
+  if (N == 0) return 0;
+  BJX_CHECK_ARG(lam && logprior && loglik && logp_out, "bjx_smc_temper_value: null pointer");
+  hipLaunchKernelGGL(k_temper_value, dim3(flat_grid(N)), dim3(kBlock), 0, (hipStream_t)stream, N, lam, logprior,
+                     loglik, logp_out);
+  return bjx_check_launch("bjx_smc_temper_value");
 }
 
 int bjx_smc_reweight(void* stream, int64_t N, const float* loglik, const float* lam_old, const float* lam_new,

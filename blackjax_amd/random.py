@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["key", "PRNGKey", "split", "fold_in", "uniform", "key_words", "ChainMajorKey", "key_spec"]
+__all__ = ["key", "PRNGKey", "split", "fold_in", "uniform", "key_words", "ChainMajorKey", "key_spec", "chain_normal"]
 
 
 def key(seed: int) -> np.ndarray:
@@ -84,3 +84,28 @@ def key_spec(rng_key) -> tuple[int, int, int]:
         return k0, k1, rng_key.step
     k0, k1 = key_words(rng_key)
     return k0, k1, -1
+
+
+def chain_normal(rng_key, n_chains: int, dim: int, *, device, chain_offset: int = 0, child=None):
+    """``(n_chains, dim)`` float32 device tensor whose row ``i`` is ``jax.random.normal(k, (dim,))`` with ``k`` chain
+    ``i``'s key: ``split(rng_key, .)[chain_offset + i]``, or its step-fold child for a ``ChainMajorKey``.  With
+    ``child=0`` or ``child=1``, ``k`` is that child of ``split(k, 2)``; ``child=0`` is the reference's ``key_proposal``
+    of an ``rmh`` / ``irmh`` transition.  For user-written proposal generators, which receive the transition's
+    ``rng_key`` unchanged (``bjx_rw_noise``)."""
+    import torch
+
+    if child not in (None, 0, 1):
+        raise ValueError(f"child must be None, 0 or 1, got {child!r}")
+    n_chains, dim = int(n_chains), int(dim)
+    if n_chains < 0 or dim < 1:
+        raise ValueError(f"chain_normal needs n_chains >= 0 and dim >= 1, got {n_chains} and {dim}")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"chain_normal draws on {device}: blackjax_amd runs on ROCm devices only "
+                           "(there is no CPU fallback)")
+    k0, k1, fold = key_spec(rng_key)
+    out = torch.empty((n_chains, dim), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _lib.call("bjx_rw_noise", _lib.current_stream(), k0, k1, int(chain_offset), fold,
+                  -1 if child is None else int(child), n_chains, dim, out.data_ptr())
+    return out

@@ -31,7 +31,7 @@ from typing import Callable, NamedTuple
 import torch
 
 from .. import _lib
-from .._util import eval_logdensity, is_capturable, value_and_grad
+from .._util import eval_logdensity, eval_value, is_capturable, value_and_grad
 from ..base import SamplingAlgorithm
 from ..random import split
 from . import base
@@ -65,6 +65,7 @@ class TemperedLogDensity:
     _bjx_value_and_grad = True
 
     def __init__(self, logprior_fn: Callable, loglikelihood_fn: Callable):
+        self.logprior_fn, self.loglikelihood_fn = logprior_fn, loglikelihood_fn
         self.logprior_vg = value_and_grad(logprior_fn)
         self.loglikelihood_vg = value_and_grad(loglikelihood_fn)
         self._bjx_capturable = is_capturable(logprior_fn) and is_capturable(loglikelihood_fn)
@@ -90,6 +91,17 @@ class TemperedLogDensity:
         _lib.call("bjx_smc_temper", _lib.current_stream(), n, d, self.temperature(q.device).data_ptr(), lp.data_ptr(),
                   gp.data_ptr(), ll.data_ptr(), gl.data_ptr(), logp.data_ptr(), grad.data_ptr())
         return logp, grad
+
+    def _bjx_value(self, q: torch.Tensor) -> torch.Tensor:
+        """The value alone (``_util.eval_value``): both callables evaluated value-only, combined by
+        ``bjx_smc_temper_value`` with the arithmetic ``bjx_smc_temper`` uses for ``logp`` -- bit-equal to
+        ``self(q)[0]`` whenever the callables' values are.  What a gradient-free inner kernel pays per move."""
+        lp = eval_value(self.logprior_fn, q)
+        ll = eval_value(self.loglikelihood_fn, q)
+        logp = torch.empty_like(lp)
+        _lib.call("bjx_smc_temper_value", _lib.current_stream(), q.shape[0], self.temperature(q.device).data_ptr(),
+                  lp.data_ptr(), ll.data_ptr(), logp.data_ptr())
+        return logp
 
 
 def build_kernel(logprior_fn: Callable, loglikelihood_fn: Callable, mcmc_step_fn: Callable, mcmc_init_fn: Callable,

@@ -545,6 +545,36 @@ int bjx_ess_shrink(void* stream, uint32_t key0, uint32_t key1, int64_t chain_off
                    uint8_t* done, float* q_prop, float* logdensity_out, float* theta_out, int32_t* subiter_out,
                    float* momentum_out, int32_t* n_live);
 
+/* ---- random walk (blackjax.rmh / additive_step_random_walk / irmh; blackjax/mcmc/random_walk.py, irmh.py) ----
+ * Gradient-free Metropolis-Hastings.  One transition = a proposal (bjx_rw_propose, or a user generator) -> user
+ * callable at q1, VALUE ONLY -> bjx_rw_finish.  Keys:
+ *   k_i = split(key, .)[chain_offset+i] (or its step_fold child) ; key_proposal, key_accept = split(k_i, 2)
+ *
+ * out[i] = normal(k, (D,)) with k = k_i (child == -1) or split(k_i, 2)[child] (child 0 or 1): what
+ * random.chain_normal hands a user-written generator, and the left operand of the dense step's product. */
+int bjx_rw_noise(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int32_t child,
+                 int64_t N, int64_t D, float* out);
+/* The Gaussian random step added to the position, out of place.  At most one of sigma_diag (D,) and move_lin (N, D):
+ *   q1 = fma(s_j, normal(key_proposal, (D,))[j], q0), s_j = sigma_diag[j] or the scalar sigma    (scalar / diagonal)
+ *   q1 = q0 + move_lin, move_lin = normal(key_proposal, (D,)) @ sigma^T from bjx_rw_noise(child 0) +
+ *        bjx_dense_matmul, i.e. row i = sigma @ z_i                                               (dense)
+ * Replaces: mcmc/random_walk.py::normal (propose) and build_additive_step (the sum), util.py::generate_gaussian_noise. */
+int bjx_rw_propose(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int64_t N,
+                   int64_t D, float sigma, const float* sigma_diag, const float* move_lin, const float* q0,
+                   float* q1_out);
+/* Metropolis-Hastings accept + state select, out of place.  f_init_prop[i] = log-density of proposing q1 from q0,
+ * f_prop_init[i] = of proposing q0 from q1; both null for a symmetric proposal (exactly one null is an error):
+ *   e_init = (-logp0) - f_init_prop ; e_new = (-logp1) - f_prop_init         (transition_energy; -logp without f)
+ *   delta = e_init - e_new (NaN -> -inf) ; p_acc = min(1, exp(delta))
+ *   accept = uniform(key_accept) < p_acc ; (q, logp)_out = accept ? (q1, logp1) : (q0, logp0)
+ * Only the chosen source row is read.  is_accepted_out: one byte per chain, 0 / 1.
+ * Replaces: mcmc/random_walk.py::build_rmh (transition_energy, kernel, rmh_proposal), mcmc/irmh.py::build_kernel ;
+ * mcmc/proposal.py::compute_asymmetric_acceptance_ratio, static_binomial_sampling, safe_energy_diff. */
+int bjx_rw_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int64_t N,
+                  int64_t D, const float* q0, const float* logp0, const float* q1, const float* logp1,
+                  const float* f_init_prop, const float* f_prop_init, float* q_out, float* logp_out,
+                  float* acceptance_rate_out, uint8_t* is_accepted_out);
+
 /* ---- SMC (blackjax.tempered_smc / adaptive_tempered_smc; blackjax/smc/) -----------------------
  * One step = bjx_smc_resample -> bjx_smc_gather -> num_mcmc_steps transitions of an MCMC kernel on the tempered
  * log-density (bjx_smc_temper after the two user callables) -> user log-likelihood -> bjx_smc_reweight; the adaptive
@@ -575,6 +605,11 @@ int bjx_smc_gather(void* stream, int64_t N, int64_t num_samples, int64_t D, cons
 int bjx_smc_temper(void* stream, int64_t N, int64_t D, const float* lam, const float* logprior,
                    const float* logprior_grad, const float* loglik, const float* loglik_grad, float* logp_out,
                    float* grad_out);
+/* The value alone, for samplers that take no gradient: logp_out = logprior + lam * loglik over (N,), the same
+ * rounded product and rounded sum as bjx_smc_temper's logp_out (bit-equal to it).  One launch.
+ * Replaces: smc/tempered.py::build_kernel (tempered_logposterior_fn). */
+int bjx_smc_temper_value(void* stream, int64_t N, const float* lam, const float* logprior, const float* loglik,
+                         float* logp_out);
 /* lw = (*lam_new - *lam_old) * loglik (0 when the difference is 0, whatever loglik is); a NaN or -inf lw is a
  * particle of weight 0.  lse = logsumexp(lw) (fp64) ; weights_out = exp(lw - lse) ;
  * *log_likelihood_increment_out = lse - log N ; *lam_out = *lam_new.  No particle of positive weight: weights NaN,
