@@ -8,18 +8,11 @@
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 
 using namespace bjx;
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
-
-__device__ __forceinline__ int64_t wave_row0() {
-  return (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-}
-__device__ __forceinline__ int64_t wave_row_stride() { return (int64_t)gridDim.x * kWavesPerBlock; }
 
 __device__ __forceinline__ float log_cr(float x) { return (float)log((double)x); }
 
@@ -197,20 +190,16 @@ int bjx_welford_update_diag(void* stream, int64_t N, int64_t D, int64_t sample_s
   BJX_CHECK_ARG(N >= 0 && D > 0 && sample_size_new >= 1 && value && mean_in && m2_in && mean_out &&
                     m2_out,
                 "bjx_welford_update_diag: bad arguments");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
   const float n = (float)sample_size_new;
-  if (bjx_vec4_ok(D, value, mean_in, m2_in, mean_out, m2_out) && (D / 4) % 64 != 0) {
+  const bool v4 = bjx_vec4_ok(D, value, mean_in, m2_in, mean_out, m2_out);
+  if (v4 && (D / 4) % 64 != 0) {
     const int64_t total4 = N * (D / 4);
     int64_t blocks = (total4 + kBlock - 1) / kBlock;
     if (blocks > 256 * 64) blocks = 256 * 64;
-    hipLaunchKernelGGL(k_welford_update_flat, dim3((unsigned)blocks), block, 0, (hipStream_t)stream, total4,
+    hipLaunchKernelGGL(k_welford_update_flat, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, total4,
                        n, value, mean_in, m2_in, mean_out, m2_out);
-  } else if (bjx_vec4_ok(D, value, mean_in, m2_in, mean_out, m2_out))
-    hipLaunchKernelGGL(k_welford_update_diag<4>, grid, block, 0, (hipStream_t)stream, N, D, n, value,
-                       mean_in, m2_in, mean_out, m2_out);
-  else
-    hipLaunchKernelGGL(k_welford_update_diag<1>, grid, block, 0, (hipStream_t)stream, N, D, n, value,
-                       mean_in, m2_in, mean_out, m2_out);
+  } else
+    BJX_LAUNCH_ROWS_VEC(v4, k_welford_update_diag, N, stream, N, D, n, value, mean_in, m2_in, mean_out, m2_out);
   return bjx_check_launch("bjx_welford_update_diag");
 }
 

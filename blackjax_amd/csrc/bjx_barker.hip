@@ -4,41 +4,18 @@
 // diagonal preconditioner, mcmc/proposal.py::compute_asymmetric_acceptance_ratio, static_binomial_sampling,
 // safe_energy_diff.  Livingstone & Zanella 2022.
 //
-// Same layout and mapping as bjx_mala.hip: (N, D) row-major fp32, one wavefront owns one chain row at a time,
-// lanes sweep the row in 16-byte pieces (4-byte sweeps when D % 4 != 0 or a pointer is not 16-byte aligned).
-// A transition is propose -> user callable -> finish: 12 (16 with a per-chain metric) + 8 + 24 bytes per element.
+// Layout and mapping: bjx_rows.h.  A transition is propose -> user callable -> finish:
+// 12 (16 with a per-chain metric) + 8 + 24 bytes per element.
 #include <math.h>
 
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 
 using namespace bjx;
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
-
-__device__ __forceinline__ int64_t wave_row0() {
-  return (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-}
-__device__ __forceinline__ int64_t wave_row_stride() { return (int64_t)gridDim.x * kWavesPerBlock; }
-
-template <int VEC>
-__device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const F4 t = ld4(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) st4(p, F4{v[0], v[1], v[2], v[3]});
-  else p[0] = v[0];
-}
 
 // jax.scipy.special.expit in fp64, rounded once to fp32 (the oracle's expit_cr)
 __device__ __forceinline__ float expit_cr(float x) { return (float)(1.0 / (1.0 + exp(-(double)x))); }
@@ -77,14 +54,7 @@ k_barker_propose(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, float
 #pragma unroll
         for (int e = 0; e < VEC; ++e) mm[e] = 1.0f;
       }
-      if constexpr (VEC == 4) {
-        uint32_t bits[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) bits[e] = key_bits32(kn, (uint64_t)(j + e));
-        normal4_from_bits(bits, n);
-      } else {
-        n[0] = normal_from_bits(key_bits32(kn, (uint64_t)j));
-      }
+      normalv<VEC>(kn, j, n);
 #pragma unroll
       for (int e = 0; e < VEC; ++e) {
         const float u = unit_float(key_bits32(ku, (uint64_t)(j + e)));  // uniform(k2, (D,))[j + e]
@@ -107,18 +77,12 @@ __device__ __forceinline__ double barker_term(float a0, float a1, float b0, floa
   return softplus64(a) - softplus64(e);
 }
 
-// The per-chain scalar tail (every lane computes it; lane 0 writes): compute_asymmetric_acceptance_ratio on
-// safe_energy_diff, static_binomial_sampling -- the draw and compare of k_mala_finish with
-// key_rmh = split(chain key, 2)[1].
+// The per-chain scalar tail (every lane computes it; lane 0 writes): metropolis_accept on safe_energy_diff of the
+// log ratio, key_rmh = split(chain key, 2)[1].
 __device__ __forceinline__ bool barker_accept(Key key, int64_t gidx, int64_t fold, double sum, float lp0,
                                               float lp1, float* p_acc_out) {
-  float log_ratio = (lp1 - lp0) + (float)sum;
-  if (log_ratio != log_ratio) log_ratio = -__builtin_inff();  // safe_energy_diff
-  const float p_acc = fminf(exp_cr(log_ratio), 1.0f);
-  const Key kc = chain_key(key, (uint64_t)gidx, fold);
-  const float u = key_uniform(key_child(kc, 1));
-  *p_acc_out = p_acc;
-  return u < p_acc;
+  const float log_ratio = (lp1 - lp0) + (float)sum;
+  return metropolis_accept(key, gidx, fold, safe_energy_diff(log_ratio), p_acc_out);
 }
 
 // General two-pass finish.  Pass 1 sweeps q0, q1, g0, g1 once and accumulates the fp64 sum; pass 2 copies the
@@ -228,14 +192,8 @@ int bjx_barker_propose(void* stream, uint32_t key0, uint32_t key1, int64_t chain
   if (N == 0) return 0;
   BJX_CHECK_ARG(q0 && g0 && q1_out, "bjx_barker_propose: null pointer");
   BJX_CHECK_ARG(!imm || imm_row_stride == 0 || imm_row_stride == D, "bjx_barker_propose: bad imm stride");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-  if (bjx_vec4_ok(D, q0, g0, q1_out, imm))
-    hipLaunchKernelGGL(k_barker_propose<4>, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N,
-                       D, tau, tau_per_chain, imm, imm_row_stride, q0, g0, q1_out);
-  else
-    hipLaunchKernelGGL(k_barker_propose<1>, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N,
-                       D, tau, tau_per_chain, imm, imm_row_stride, q0, g0, q1_out);
+  BJX_LAUNCH_ROWS_VEC(bjx_vec4_ok(D, q0, g0, q1_out, imm), k_barker_propose, N, stream, Key{key0, key1},
+                      chain_offset, step_fold, N, D, tau, tau_per_chain, imm, imm_row_stride, q0, g0, q1_out);
   return bjx_check_launch("bjx_barker_propose");
 }
 
@@ -248,11 +206,9 @@ int bjx_barker_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_
   BJX_CHECK_ARG(q0 && logp0 && g0 && q1 && logp1 && g1 && q_out && logp_out && g_out && acceptance_rate_out &&
                     is_accepted_out,
                 "bjx_barker_finish: null pointer");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-#define BJX_BARKER_FINISH(KERNEL)                                                                              \
-  hipLaunchKernelGGL(KERNEL, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N, D, q0, logp0, \
-                     g0, q1, logp1, g1, q_out, logp_out, g_out, acceptance_rate_out, is_accepted_out)
+#define BJX_BARKER_FINISH(KERNEL)                                                                          \
+  BJX_LAUNCH_ROWS(KERNEL, N, stream, Key{key0, key1}, chain_offset, step_fold, N, D, q0, logp0, g0, q1, logp1, \
+                  g1, q_out, logp_out, g_out, acceptance_rate_out, is_accepted_out)
   if (bjx_vec4_ok(D, q0, g0, q1, g1, q_out, g_out)) {
     if (D <= 256) BJX_BARKER_FINISH(k_barker_finish_res<1>);
     else if (D <= 512) BJX_BARKER_FINISH(k_barker_finish_res<2>);

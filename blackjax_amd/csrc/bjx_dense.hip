@@ -12,6 +12,7 @@
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 
 using namespace bjx;
 
@@ -530,13 +531,6 @@ __global__ void __launch_bounds__(kThreads8) k_dense_gemm_tn8(GemmArgs a) {
 #endif
 }
 
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
-__device__ __forceinline__ int64_t wave_row0() {
-  return (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-}
-__device__ __forceinline__ int64_t wave_row_stride() { return (int64_t)gridDim.x * kWavesPerBlock; }
-
 // z = normal(km, (D,)), km = split(chain key, 2)[0]   (util.py:89-90)
 __global__ void __launch_bounds__(kBlock)
 k_dense_z(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, float* __restrict__ z) {
@@ -585,12 +579,10 @@ k_hmc_finish_dense(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, flo
     const float lp0 = logp0[r], lp1 = logp1[r];
     const float H0 = -lp0 + ke0[r];
     const float H1 = -lp1 + ke1;
-    float delta = H0 - H1;
-    if (delta != delta) delta = -__builtin_inff();
+    const float delta = safe_energy_diff(H0 - H1);
     const bool is_div = (-delta) > thr;
-    const float p_acc = fminf(exp_cr(delta), 1.0f);
-    const Key ki = key_child(chain_key(key, (uint64_t)(r + off), fold), 1);
-    const bool accept = key_uniform(ki) < p_acc;
+    float p_acc;
+    const bool accept = metropolis_accept(key, r + off, fold, delta, &p_acc);
     if (lane == 0) {
       logp_out[r] = accept ? lp1 : lp0;
       acc_rate_out[r] = p_acc;
@@ -631,8 +623,7 @@ k_mhmc_step_dense(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, int6
     const float lp = logp_new[r];
     const float H0 = -logp0[r] + ke0[r];
     const float e_new = -lp + ke;
-    float w = H0 - e_new;
-    if (w != w) w = -__builtin_inff();
+    const float w = safe_energy_diff(H0 - e_new);
     const float s_new = fminf(w, 0.0f);
     const bool is_div = (-w) > thr;
     const float Wc = W[r];

@@ -3,9 +3,7 @@
 // Reference: blackjax/mcmc/elliptical_slice.py (init, build_kernel: kernel, elliptical_proposal: slice_fn, ellipsis),
 // blackjax/util.py::generate_gaussian_noise.
 //
-// Same layout and mapping as bjx_mala.hip: (N, D) row-major fp32, one wavefront owns one chain row at a time,
-// lanes sweep the row in 16-byte pieces (4-byte sweeps when D % 4 != 0 or a pointer is not 16-byte aligned);
-// per-row scalars are computed by every lane and written by lane 0.  A transition is
+// Layout and mapping: bjx_rows.h.  A transition is
 //   begin -> user callable -> { shrink -> user callable } until no chain is live.
 // Bytes per element: begin (diagonal prior) 4 read + 8 written and one normal draw -- bjx_mala_propose's profile;
 // begin (dense prior) 8 + 8; shrink of a live row 8 read + 4 written; shrink of a row that accepts 8 read + 4
@@ -15,46 +13,11 @@
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 
 using namespace bjx;
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
-
-__device__ __forceinline__ int64_t wave_row0() {
-  return (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-}
-__device__ __forceinline__ int64_t wave_row_stride() { return (int64_t)gridDim.x * kWavesPerBlock; }
-
-template <int VEC>
-__device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const F4 t = ld4(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) st4(p, F4{v[0], v[1], v[2], v[3]});
-  else p[0] = v[0];
-}
-
-// normal(key, (D,))[j .. j + VEC)
-template <int VEC>
-__device__ __forceinline__ void normalv(Key kn, int64_t j, float (&z)[VEC]) {
-  if constexpr (VEC == 4) {
-    uint32_t bits[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) bits[e] = key_bits32(kn, (uint64_t)(j + e));
-    normal4_from_bits(bits, z);
-  } else {
-    z[0] = normal_from_bits(key_bits32(kn, (uint64_t)j));
-  }
-}
 
 // The four keys of a transition: key_slice, key_momentum, key_uniform, key_theta = split(chain key, 4).
 enum { kKeySlice = 0, kKeyMomentum = 1, kKeyUniform = 2, kKeyTheta = 3 };
@@ -219,12 +182,10 @@ int bjx_ess_begin(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offs
                 "bjx_ess_begin: null pointer");
   BJX_CHECK_ARG((cov_diag != nullptr) != (nu_lin != nullptr),
                 "bjx_ess_begin: exactly one of cov_diag and nu_lin must be given");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-#define BJX_ESS_BEGIN(VEC, DENSE)                                                                               \
-  hipLaunchKernelGGL((k_ess_begin<VEC, DENSE>), grid, block, 0, (hipStream_t)stream, key, chain_offset,         \
-                     step_fold, N, D, mean, cov_diag, nu_lin, q0, logp0, nu_out, q_prop_out, logy_out, theta_out, \
-                     theta_min_out, theta_max_out, subiter_out, done_out)
+#define BJX_ESS_BEGIN(VEC, DENSE)                                                                                 \
+  BJX_LAUNCH_ROWS((k_ess_begin<VEC, DENSE>), N, stream, Key{key0, key1}, chain_offset, step_fold, N, D, mean,     \
+                  cov_diag, nu_lin, q0, logp0, nu_out, q_prop_out, logy_out, theta_out, theta_min_out, theta_max_out, \
+                  subiter_out, done_out)
   const bool v4 = bjx_vec4_ok(D, mean, cov_diag, nu_lin, q0, nu_out, q_prop_out);
   if (nu_lin) {
     if (v4) BJX_ESS_BEGIN(4, true);
@@ -242,12 +203,8 @@ int bjx_ess_noise(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offs
   BJX_CHECK_ARG(N >= 0 && D > 0, "bjx_ess_noise: bad sizes");
   if (N == 0) return 0;
   BJX_CHECK_ARG(n_out, "bjx_ess_noise: null pointer");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-  if (bjx_vec4_ok(D, n_out))
-    hipLaunchKernelGGL(k_ess_noise<4>, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N, D, n_out);
-  else
-    hipLaunchKernelGGL(k_ess_noise<1>, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N, D, n_out);
+  BJX_LAUNCH_ROWS_VEC(bjx_vec4_ok(D, n_out), k_ess_noise, N, stream, Key{key0, key1}, chain_offset, step_fold, N, D,
+                      n_out);
   return bjx_check_launch("bjx_ess_noise");
 }
 
@@ -261,15 +218,9 @@ int bjx_ess_shrink(void* stream, uint32_t key0, uint32_t key1, int64_t chain_off
   BJX_CHECK_ARG(mean && q0 && nu && logp_prop && logy && theta && theta_min && theta_max && subiter && done &&
                     q_prop && logdensity_out && theta_out && subiter_out && momentum_out && n_live,
                 "bjx_ess_shrink: null pointer");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-#define BJX_ESS_SHRINK(VEC)                                                                                      \
-  hipLaunchKernelGGL(k_ess_shrink<VEC>, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N, D, \
-                     mean, q0, nu, logp_prop, logy, theta, theta_min, theta_max, subiter, done, q_prop,          \
-                     logdensity_out, theta_out, subiter_out, momentum_out, n_live)
-  if (bjx_vec4_ok(D, mean, q0, nu, q_prop, momentum_out)) BJX_ESS_SHRINK(4);
-  else BJX_ESS_SHRINK(1);
-#undef BJX_ESS_SHRINK
+  BJX_LAUNCH_ROWS_VEC(bjx_vec4_ok(D, mean, q0, nu, q_prop, momentum_out), k_ess_shrink, N, stream, Key{key0, key1},
+                      chain_offset, step_fold, N, D, mean, q0, nu, logp_prop, logy, theta, theta_min, theta_max,
+                      subiter, done, q_prop, logdensity_out, theta_out, subiter_out, momentum_out, n_live);
   return bjx_check_launch("bjx_ess_shrink");
 }
 

@@ -1,41 +1,18 @@
 // Generalized HMC (persistent momentum, non-reversible slice accept) for a diagonal momentum metric
 // (gfx950).  C ABI in include/bjx_ghmc.h; reference lines cited there.
 //
-// Same layout and mapping as bjx_hmc.hip: (N, D) row-major fp32, one wavefront owns one chain row at a
-// time, lanes sweep the row in 16-byte pieces.  A transition is ONE leapfrog, so these kernels together
-// move ~16 words per element and transition against the leapfrog's 5: memory-bound streams.
+// Layout and mapping: bjx_rows.h.  A transition is ONE leapfrog, so these kernels together move ~16 words
+// per element and transition against the leapfrog's 5: memory-bound streams.
 #include <math.h>
 
 #include "../../include/bjx_ghmc.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 
 using namespace bjx;
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
-
-__device__ __forceinline__ int64_t wave_row0() {
-  return (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-}
-__device__ __forceinline__ int64_t wave_row_stride() { return (int64_t)gridDim.x * kWavesPerBlock; }
-
-template <int VEC>
-__device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const F4 t = ld4(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) st4(p, F4{v[0], v[1], v[2], v[3]});
-  else p[0] = v[0];
-}
 
 // ghmc.py:53-64
 template <int VEC>
@@ -179,8 +156,7 @@ k_ghmc_finish(int64_t N, int64_t D, float eps_s, const float* __restrict__ eps_p
     const float lp0 = logp0[r], lp1 = logp1[r];
     const float H0 = -lp0 + ke0[r];
     const float H1 = -lp1 + ke1;
-    float dE = H0 - H1;
-    if (dE != dE) dE = -__builtin_inff();  // proposal.py:45-48
+    const float dE = safe_energy_diff(H0 - H1);
     const bool is_div = (-dE) > thr;
     const float p_acc = fminf(exp_cr(dE), 1.0f);
     const float s = sl[r];
@@ -279,8 +255,7 @@ k_ghmc_finish_res(int64_t N, int64_t D, float eps_s, const float* __restrict__ e
     const float lp0 = logp0[r], lp1 = logp1[r];
     const float H0 = -lp0 + ke0[r];
     const float H1 = -lp1 + ke1;
-    float dE = H0 - H1;
-    if (dE != dE) dE = -__builtin_inff();
+    const float dE = safe_energy_diff(H0 - H1);
     const bool is_div = (-dE) > thr;
     const float p_acc = fminf(exp_cr(dE), 1.0f);
     const float s = sl[r];
@@ -332,14 +307,8 @@ int bjx_ghmc_init(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offs
   BJX_CHECK_ARG(N >= 0 && D > 0, "bjx_ghmc_init: bad sizes");
   if (N == 0) return 0;
   BJX_CHECK_ARG(momentum_out && slice_out, "bjx_ghmc_init: null pointer");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-  if (bjx_vec4_ok(D, momentum_out))
-    hipLaunchKernelGGL(k_ghmc_init<4>, grid, block, 0, (hipStream_t)stream, key, chain_offset, N, D,
-                       momentum_out, slice_out);
-  else
-    hipLaunchKernelGGL(k_ghmc_init<1>, grid, block, 0, (hipStream_t)stream, key, chain_offset, N, D,
-                       momentum_out, slice_out);
+  BJX_LAUNCH_ROWS_VEC(bjx_vec4_ok(D, momentum_out), k_ghmc_init, N, stream, Key{key0, key1}, chain_offset, N, D,
+                      momentum_out, slice_out);
   return bjx_check_launch("bjx_ghmc_init");
 }
 
@@ -352,20 +321,15 @@ int bjx_ghmc_refresh(void* stream, uint32_t key0, uint32_t key1, int64_t chain_o
   if (N == 0) return 0;
   BJX_CHECK_ARG(imm && p_prev && slice_prev && p_out && slice_out && ke_out, "bjx_ghmc_refresh: null pointer");
   BJX_CHECK_ARG(imm_stride == 0 || imm_stride == D, "bjx_ghmc_refresh: imm_stride must be 0 or D");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-#define BJX_REFRESH(V)                                                                                   \
-  hipLaunchKernelGGL((k_ghmc_refresh<V, false>), grid, block, 0, (hipStream_t)stream, key, chain_offset,   \
-                     step_fold, N, D, imm, imm_stride, alpha, alpha_per_chain, delta, delta_per_chain,     \
-                     p_prev, slice_prev, p_out, slice_out, ke_out, 0.0f, nullptr, nullptr, nullptr,        \
-                     nullptr, nullptr)
-  if (bjx_vec4_ok(D, imm, p_prev, p_out) && imm_stride == 0 && D <= 1024 && N >= 4096)
-    hipLaunchKernelGGL((k_ghmc_refresh<4, false, true>), dim3(bjx_row_grid((N + 3) / 4, kWavesPerBlock)), block, 0,
-                       (hipStream_t)stream, key, chain_offset, step_fold, N, D, imm, imm_stride, alpha, alpha_per_chain,
-                       delta, delta_per_chain, p_prev, slice_prev, p_out, slice_out, ke_out, 0.0f, nullptr, nullptr,
-                       nullptr, nullptr, nullptr);
-  else if (bjx_vec4_ok(D, imm, p_prev, p_out)) BJX_REFRESH(4);
-  else BJX_REFRESH(1);
+  // HOIST: a quarter of the waves, each sweeping several rows
+#define BJX_REFRESH(ROWS, V, HOIST)                                                                            \
+  BJX_LAUNCH_ROWS((k_ghmc_refresh<V, false, HOIST>), ROWS, stream, Key{key0, key1}, chain_offset, step_fold, N, D, \
+                  imm, imm_stride, alpha, alpha_per_chain, delta, delta_per_chain, p_prev, slice_prev, p_out,  \
+                  slice_out, ke_out, 0.0f, nullptr, nullptr, nullptr, nullptr, nullptr)
+  const bool v4 = bjx_vec4_ok(D, imm, p_prev, p_out);
+  if (v4 && imm_stride == 0 && D <= 1024 && N >= 4096) BJX_REFRESH((N + 3) / 4, 4, true);
+  else if (v4) BJX_REFRESH(N, 4, false);
+  else BJX_REFRESH(N, 1, false);
 #undef BJX_REFRESH
   return bjx_check_launch("bjx_ghmc_refresh");
 }
@@ -381,20 +345,14 @@ int bjx_ghmc_refresh_kick(void* stream, uint32_t key0, uint32_t key1, int64_t ch
   BJX_CHECK_ARG(imm && p_prev && slice_prev && q0 && g0 && p_out && slice_out && ke_out && q1_out && p_half_out,
                 "bjx_ghmc_refresh_kick: null pointer");
   BJX_CHECK_ARG(imm_stride == 0 || imm_stride == D, "bjx_ghmc_refresh_kick: imm_stride must be 0 or D");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-#define BJX_REFRESH_KICK(V)                                                                              \
-  hipLaunchKernelGGL((k_ghmc_refresh<V, true>), grid, block, 0, (hipStream_t)stream, key, chain_offset,    \
-                     step_fold, N, D, imm, imm_stride, alpha, alpha_per_chain, delta, delta_per_chain,     \
-                     p_prev, slice_prev, p_out, slice_out, ke_out, eps, eps_per_chain, q0, g0, q1_out,     \
-                     p_half_out)
-  if (bjx_vec4_ok(D, imm, p_prev, p_out, q0, g0, q1_out, p_half_out) && imm_stride == 0 && D <= 1024 && N >= 4096)
-    hipLaunchKernelGGL((k_ghmc_refresh<4, true, true>), dim3(bjx_row_grid((N + 3) / 4, kWavesPerBlock)), block, 0,
-                       (hipStream_t)stream, key, chain_offset, step_fold, N, D, imm, imm_stride, alpha, alpha_per_chain,
-                       delta, delta_per_chain, p_prev, slice_prev, p_out, slice_out, ke_out, eps, eps_per_chain, q0, g0,
-                       q1_out, p_half_out);
-  else if (bjx_vec4_ok(D, imm, p_prev, p_out, q0, g0, q1_out, p_half_out)) BJX_REFRESH_KICK(4);
-  else BJX_REFRESH_KICK(1);
+#define BJX_REFRESH_KICK(ROWS, V, HOIST)                                                                      \
+  BJX_LAUNCH_ROWS((k_ghmc_refresh<V, true, HOIST>), ROWS, stream, Key{key0, key1}, chain_offset, step_fold, N, D, \
+                  imm, imm_stride, alpha, alpha_per_chain, delta, delta_per_chain, p_prev, slice_prev, p_out, \
+                  slice_out, ke_out, eps, eps_per_chain, q0, g0, q1_out, p_half_out)
+  const bool v4 = bjx_vec4_ok(D, imm, p_prev, p_out, q0, g0, q1_out, p_half_out);
+  if (v4 && imm_stride == 0 && D <= 1024 && N >= 4096) BJX_REFRESH_KICK((N + 3) / 4, 4, true);
+  else if (v4) BJX_REFRESH_KICK(N, 4, false);
+  else BJX_REFRESH_KICK(N, 1, false);
 #undef BJX_REFRESH_KICK
   return bjx_check_launch("bjx_ghmc_refresh_kick");
 }
@@ -415,26 +373,19 @@ int bjx_ghmc_finish(void* stream, int64_t N, int64_t D, float eps, const float* 
                 "bjx_ghmc_finish: null pointer");
   BJX_CHECK_ARG(imm_stride == 0 || imm_stride == D, "bjx_ghmc_finish: imm_stride must be 0 or D");
   BJX_CHECK_ARG(skip_begin <= skip_end, "bjx_ghmc_finish: skip_begin must not exceed skip_end");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-#define BJX_FINISH(V)                                                                                     \
-  hipLaunchKernelGGL(k_ghmc_finish<V>, grid, block, 0, (hipStream_t)stream, N, D, eps, eps_per_chain, imm,  \
-                     imm_stride, divergence_threshold, q0, logp0, g0, ke0, p, slice, p_prev, slice_prev,    \
-                     q1, p_half, logp1, g1, skip_begin, skip_end, q_out, p_out, logp_out, g_out, slice_out, \
-                     acceptance_rate_out, is_accepted_out, is_divergent_out, energy_out, p_end_out)
-#define BJX_FINISH_RES(NI_)                                                                                  \
-  hipLaunchKernelGGL(k_ghmc_finish_res<NI_>, grid, block, 0, (hipStream_t)stream, N, D, eps, eps_per_chain,     \
-                     imm, imm_stride, divergence_threshold, q0, logp0, g0, ke0, p, slice, p_prev, slice_prev,  \
-                     q1, p_half, logp1, g1, skip_begin, skip_end, q_out, p_out, logp_out, g_out, slice_out,    \
-                     acceptance_rate_out, is_accepted_out, is_divergent_out, energy_out, p_end_out)
+#define BJX_FINISH(KERNEL)                                                                                      \
+  BJX_LAUNCH_ROWS(KERNEL, N, stream, N, D, eps, eps_per_chain, imm, imm_stride, divergence_threshold, q0, logp0, g0, \
+                  ke0, p, slice, p_prev, slice_prev, q1, p_half, logp1, g1, skip_begin, skip_end, q_out, p_out,      \
+                  logp_out, g_out, slice_out, acceptance_rate_out, is_accepted_out, is_divergent_out, energy_out,    \
+                  p_end_out)
   if (bjx_vec4_ok(D, imm, q0, g0, p, p_prev, q1, p_half, g1, q_out, p_out, g_out, p_end_out)) {
-    if (D <= 256) BJX_FINISH_RES(1);
-    else if (D <= 512) BJX_FINISH_RES(2);
-    else if (D <= 1024) BJX_FINISH_RES(4);
-    else BJX_FINISH(4);
+    if (D <= 256) BJX_FINISH(k_ghmc_finish_res<1>);
+    else if (D <= 512) BJX_FINISH(k_ghmc_finish_res<2>);
+    else if (D <= 1024) BJX_FINISH(k_ghmc_finish_res<4>);
+    else BJX_FINISH(k_ghmc_finish<4>);
   } else {
-    BJX_FINISH(1);
+    BJX_FINISH(k_ghmc_finish<1>);
   }
-#undef BJX_FINISH_RES
 #undef BJX_FINISH
   return bjx_check_launch("bjx_ghmc_finish");
 }

@@ -1,11 +1,11 @@
 // HMC transition kernels for a diagonal metric (gfx950).  C ABI in include/bjx_hip.h.
 //
-// Layout: (N, D) row-major fp32, one wavefront owns one chain row at a time
-// (grid-stride over rows), lanes sweep the row in 16-byte pieces so every wave
-// instruction moves 1 KiB of contiguous HBM.  All kernels are HBM-bound streams.
+// Layout and mapping: bjx_rows.h; with 16-byte pieces every wave instruction moves 1 KiB of contiguous
+// HBM.  All kernels are HBM-bound streams.
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 
 using namespace bjx;
 
@@ -14,14 +14,6 @@ namespace {
 #ifndef BJX_REVERSE_ROWS
 #define BJX_REVERSE_ROWS 1
 #endif
-
-constexpr int kBlock = 256;                 // 4 waves per workgroup
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
-
-__device__ __forceinline__ int64_t wave_row0() {
-  return (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-}
-__device__ __forceinline__ int64_t wave_row_stride() { return (int64_t)gridDim.x * kWavesPerBlock; }
 
 // ------------------------------------------------------------------------------ RNG probes
 __global__ void __launch_bounds__(kBlock) k_rng_normal(Key key, int64_t off, int64_t N, int64_t D,
@@ -464,14 +456,10 @@ k_hmc_finish_diag(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, floa
     const float lp0 = logp0[r], lp1 = logp1[r];
     const float H0 = -lp0 + ke0[r];
     const float H1 = -lp1 + ke1;
-    float delta = H0 - H1;
-    if (delta != delta) delta = -__builtin_inff();  // proposal.py:45-48
-    const bool is_div = (-delta) > thr;              // hmc.py:162
-    const float p_acc = fminf(exp_cr(delta), 1.0f);  // proposal.py:225
-    const Key kc = chain_key(key, (uint64_t)(r + off), fold);
-    const Key ki = key_child(kc, 1);                  // split(kc, 2)[1]
-    const float u = key_uniform(ki);
-    const bool accept = u < p_acc;                    // proposal.py:226
+    const float delta = safe_energy_diff(H0 - H1);
+    const bool is_div = (-delta) > thr;  // hmc.py:162
+    float p_acc;
+    const bool accept = metropolis_accept(key, r + off, fold, delta, &p_acc);
     if (lane == 0) {
       logp_out[r] = accept ? lp1 : lp0;
       acc_rate_out[r] = p_acc;
@@ -547,14 +535,10 @@ k_hmc_finish_diag_short(Key key, int64_t off, int64_t fold, int64_t N, int64_t D
     const float lp0 = logp0[rr], lp1 = logp1[rr];
     const float H0 = -lp0 + ke0[rr];
     const float H1 = -lp1 + ke1;
-    float delta = H0 - H1;
-    if (delta != delta) delta = -__builtin_inff();
+    const float delta = safe_energy_diff(H0 - H1);
     const bool is_div = (-delta) > thr;
-    const float p_acc = fminf(exp_cr(delta), 1.0f);
-    const Key kc = chain_key(key, (uint64_t)(rr + off), fold);
-    const Key ki = key_child(kc, 1);
-    const float u = key_uniform(ki);
-    const bool accept = u < p_acc;
+    float p_acc;
+    const bool accept = metropolis_accept(key, rr + off, fold, delta, &p_acc);
     if (!valid) continue;
     if (gl == 0) {
       logp_out[r] = accept ? lp1 : lp0;
@@ -636,8 +620,7 @@ k_mhmc_step_diag(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, int64
     const float lp = logp_new[r];
     const float H0 = -logp0[r] + ke0[r];
     const float e_new = -lp + ke;
-    float w = H0 - e_new;
-    if (w != w) w = -__builtin_inff();
+    const float w = safe_energy_diff(H0 - e_new);
     const float s_new = fminf(w, 0.0f);
     const bool is_div = (-w) > thr;
     const float Wc = W[r];
@@ -747,8 +730,7 @@ int bjx_rng_normal(void* stream, uint32_t key0, uint32_t key1, int64_t chain_off
                    int64_t D, float* z_out) {
   BJX_CHECK_ARG(N >= 0 && D >= 0 && (N == 0 || D == 0 || z_out), "bjx_rng_normal: bad arguments");
   if (N == 0 || D == 0) return 0;
-  hipLaunchKernelGGL(k_rng_normal, dim3(bjx_row_grid(N, kWavesPerBlock)), dim3(kBlock), 0,
-                     (hipStream_t)stream, Key{key0, key1}, chain_offset, N, D, z_out);
+  BJX_LAUNCH_ROWS(k_rng_normal, N, stream, Key{key0, key1}, chain_offset, N, D, z_out);
   return bjx_check_launch("bjx_rng_normal");
 }
 
@@ -790,32 +772,26 @@ int bjx_hmc_momentum_diag(void* stream, uint32_t key0, uint32_t key1, int64_t ch
   if (N == 0) return 0;  // empty batch: no buffers to check, nothing to do
   BJX_CHECK_ARG(N >= 0 && D > 0 && imm && p_out && ke_out, "bjx_hmc_momentum_diag: bad arguments");
   BJX_CHECK_ARG(imm_stride == 0 || imm_stride == D, "bjx_hmc_momentum_diag: imm_stride must be 0 or D");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-  if (bjx_vec4_ok(D, imm, p_out) && D <= 128) {
+  const bool v4 = bjx_vec4_ok(D, imm, p_out);
+#define BJX_MOM(ROWS, V, HOIST)                                                                               \
+  BJX_LAUNCH_ROWS((k_momentum_diag<V, false, HOIST>), ROWS, stream, Key{key0, key1}, chain_offset, step_fold, N, D, \
+                  imm, imm_stride, p_out, ke_out, 0.0f, nullptr, nullptr, nullptr, nullptr, nullptr)
+  if (v4 && D <= 128) {
     // G lanes per row = the smallest power of two with G * 4 >= D (at least 4): 64 / G rows per wave
-#define BJX_MOM_SHORT(G_)                                                                             \
-  hipLaunchKernelGGL(k_momentum_diag_short<G_>, dim3(bjx_row_grid((N * G_ + 63) / 64, kWavesPerBlock)), \
-                     block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N, D, imm, imm_stride, \
-                     p_out, ke_out)
+#define BJX_MOM_SHORT(G_)                                                                                      \
+  BJX_LAUNCH_ROWS(k_momentum_diag_short<G_>, (N * G_ + 63) / 64, stream, Key{key0, key1}, chain_offset, step_fold, \
+                  N, D, imm, imm_stride, p_out, ke_out)
     if (D <= 16) BJX_MOM_SHORT(4);
     else if (D <= 32) BJX_MOM_SHORT(8);
     else if (D <= 64) BJX_MOM_SHORT(16);
     else BJX_MOM_SHORT(32);
 #undef BJX_MOM_SHORT
-  } else if (bjx_vec4_ok(D, imm, p_out) && imm_stride == 0 && D <= 1024 && N >= 4096)
+  } else if (v4 && imm_stride == 0 && D <= 1024 && N >= 4096)
     // one shared metric: mass_sqrt hoisted out of the row loop, four rows per wave (k_momentum_diag, HOIST)
-    hipLaunchKernelGGL((k_momentum_diag<4, false, true>), dim3(bjx_row_grid((N + 3) / 4, kWavesPerBlock)), block, 0,
-                       (hipStream_t)stream, key, chain_offset, step_fold, N, D, imm, imm_stride, p_out, ke_out, 0.0f,
-                       nullptr, nullptr, nullptr, nullptr, nullptr);
-  else if (bjx_vec4_ok(D, imm, p_out))
-    hipLaunchKernelGGL((k_momentum_diag<4, false>), grid, block, 0, (hipStream_t)stream, key, chain_offset,
-                       step_fold, N, D, imm, imm_stride, p_out, ke_out, 0.0f, nullptr, nullptr, nullptr, nullptr,
-                       nullptr);
-  else
-    hipLaunchKernelGGL((k_momentum_diag<1, false>), grid, block, 0, (hipStream_t)stream, key, chain_offset,
-                       step_fold, N, D, imm, imm_stride, p_out, ke_out, 0.0f, nullptr, nullptr, nullptr, nullptr,
-                       nullptr);
+    BJX_MOM((N + 3) / 4, 4, true);
+  else if (v4) BJX_MOM(N, 4, false);
+  else BJX_MOM(N, 1, false);
+#undef BJX_MOM
   return bjx_check_launch("bjx_hmc_momentum_diag");
 }
 
@@ -827,20 +803,14 @@ int bjx_hmc_momentum_kick_diag(void* stream, uint32_t key0, uint32_t key1, int64
   BJX_CHECK_ARG(N >= 0 && D > 0 && imm && q0 && g0 && p_out && ke_out && q1_out && p_half_out,
                 "bjx_hmc_momentum_kick_diag: bad arguments");
   BJX_CHECK_ARG(imm_stride == 0 || imm_stride == D, "bjx_hmc_momentum_kick_diag: imm_stride must be 0 or D");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-  if (bjx_vec4_ok(D, imm, q0, g0, p_out, q1_out, p_half_out) && imm_stride == 0 && D <= 1024 && N >= 4096)
-    hipLaunchKernelGGL((k_momentum_diag<4, true, true>), dim3(bjx_row_grid((N + 3) / 4, kWavesPerBlock)), block, 0,
-                       (hipStream_t)stream, key, chain_offset, step_fold, N, D, imm, imm_stride, p_out, ke_out, eps,
-                       eps_per_chain, q0, g0, q1_out, p_half_out);
-  else if (bjx_vec4_ok(D, imm, q0, g0, p_out, q1_out, p_half_out))
-    hipLaunchKernelGGL((k_momentum_diag<4, true>), grid, block, 0, (hipStream_t)stream, key, chain_offset,
-                       step_fold, N, D, imm, imm_stride, p_out, ke_out, eps, eps_per_chain, q0, g0, q1_out,
-                       p_half_out);
-  else
-    hipLaunchKernelGGL((k_momentum_diag<1, true>), grid, block, 0, (hipStream_t)stream, key, chain_offset,
-                       step_fold, N, D, imm, imm_stride, p_out, ke_out, eps, eps_per_chain, q0, g0, q1_out,
-                       p_half_out);
+  const bool v4 = bjx_vec4_ok(D, imm, q0, g0, p_out, q1_out, p_half_out);
+#define BJX_MOM_KICK(ROWS, V, HOIST)                                                                         \
+  BJX_LAUNCH_ROWS((k_momentum_diag<V, true, HOIST>), ROWS, stream, Key{key0, key1}, chain_offset, step_fold, N, D, \
+                  imm, imm_stride, p_out, ke_out, eps, eps_per_chain, q0, g0, q1_out, p_half_out)
+  if (v4 && imm_stride == 0 && D <= 1024 && N >= 4096) BJX_MOM_KICK((N + 3) / 4, 4, true);
+  else if (v4) BJX_MOM_KICK(N, 4, false);
+  else BJX_MOM_KICK(N, 1, false);
+#undef BJX_MOM_KICK
   return bjx_check_launch("bjx_hmc_momentum_kick_diag");
 }
 
@@ -987,28 +957,18 @@ int bjx_hmc_finish_diag_coef(void* stream, uint32_t key0, uint32_t key1, int64_t
                     is_divergent_out && energy_out,
                 "bjx_hmc_finish_diag: bad arguments");
   BJX_CHECK_ARG(imm_stride == 0 || imm_stride == D, "bjx_hmc_finish_diag: imm_stride must be 0 or D");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-  hipStream_t s = (hipStream_t)stream;
-#define BJX_FIN(V)                                                                              \
-  hipLaunchKernelGGL(k_hmc_finish_diag<V>, grid, block, 0, s, key, chain_offset, step_fold, N, D, \
-                     eps,                                                                       \
-                     eps_per_chain, imm, imm_stride, divergence_threshold, q0, logp0, g0, ke0,  \
-                     q1, logp1, g1, p, p_end_out, q_out, logp_out, g_out, acceptance_rate_out,  \
-                     is_accepted_out, is_divergent_out, energy_out, kick_coef)
-  if (bjx_vec4_ok(D, imm, q0, g0, q1, g1, p, p_end_out, q_out, g_out) && D <= 128) {
-#define BJX_FIN_SHORT(G_, GRID)                                                                       \
-  hipLaunchKernelGGL(k_hmc_finish_diag_short<G_>, GRID, block, 0, s, key, chain_offset, step_fold, N, \
-                     D, eps, eps_per_chain, imm, imm_stride, divergence_threshold, q0, logp0, g0, ke0, \
-                     q1, logp1, g1, p, p_end_out, q_out, logp_out, g_out, acceptance_rate_out,        \
-                     is_accepted_out, is_divergent_out, energy_out, kick_coef)
-    if (D <= 16) BJX_FIN_SHORT(4, dim3(bjx_row_grid((N + 15) / 16, kWavesPerBlock)));
-    else if (D <= 32) BJX_FIN_SHORT(8, dim3(bjx_row_grid((N + 7) / 8, kWavesPerBlock)));
-    else if (D <= 64) BJX_FIN_SHORT(16, dim3(bjx_row_grid((N + 3) / 4, kWavesPerBlock)));
-    else BJX_FIN_SHORT(32, dim3(bjx_row_grid((N + 1) / 2, kWavesPerBlock)));
-#undef BJX_FIN_SHORT
-  } else if (bjx_vec4_ok(D, imm, q0, g0, q1, g1, p, p_end_out, q_out, g_out)) BJX_FIN(4);
-  else BJX_FIN(1);
+  const bool v4 = bjx_vec4_ok(D, imm, q0, g0, q1, g1, p, p_end_out, q_out, g_out);
+#define BJX_FIN(KERNEL, ROWS)                                                                                   \
+  BJX_LAUNCH_ROWS(KERNEL, ROWS, stream, Key{key0, key1}, chain_offset, step_fold, N, D, eps, eps_per_chain, imm, \
+                  imm_stride, divergence_threshold, q0, logp0, g0, ke0, q1, logp1, g1, p, p_end_out, q_out,     \
+                  logp_out, g_out, acceptance_rate_out, is_accepted_out, is_divergent_out, energy_out, kick_coef)
+  if (v4 && D <= 128) {  // G lanes per row, 64 / G rows per wave
+    if (D <= 16) BJX_FIN(k_hmc_finish_diag_short<4>, (N + 15) / 16);
+    else if (D <= 32) BJX_FIN(k_hmc_finish_diag_short<8>, (N + 7) / 8);
+    else if (D <= 64) BJX_FIN(k_hmc_finish_diag_short<16>, (N + 3) / 4);
+    else BJX_FIN(k_hmc_finish_diag_short<32>, (N + 1) / 2);
+  } else if (v4) BJX_FIN(k_hmc_finish_diag<4>, N);
+  else BJX_FIN(k_hmc_finish_diag<1>, N);
 #undef BJX_FIN
   return bjx_check_launch("bjx_hmc_finish_diag");
 }
@@ -1042,17 +1002,10 @@ static int mhmc_step_diag(const char* what, void* stream, uint32_t key0, uint32_
                     prop_g && prop_logp && prop_energy,
                 "bjx_mhmc_step_diag: bad arguments");
   BJX_CHECK_ARG(imm_stride == 0 || imm_stride == D, "bjx_mhmc_step_diag: imm_stride must be 0 or D");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-  hipStream_t s = (hipStream_t)stream;
-#define BJX_MH(V)                                                                               \
-  hipLaunchKernelGGL(k_mhmc_step_diag<V>, grid, block, 0, s, key, chain_offset, step_fold, N, D, \
-                     step, do_next, eps, eps_per_chain, imm, imm_stride, divergence_threshold,  \
-                     logp0, ke0, q, p, g, logp_new, weight, sum_log_p_accept, any_divergent,    \
-                     ever_accepted, prop_q, prop_p, prop_g, prop_logp, prop_energy, n_steps, kick_c, drift_c)
-  if (bjx_vec4_ok(D, imm, q, p, g, prop_q, prop_p, prop_g)) BJX_MH(4);
-  else BJX_MH(1);
-#undef BJX_MH
+  BJX_LAUNCH_ROWS_VEC(bjx_vec4_ok(D, imm, q, p, g, prop_q, prop_p, prop_g), k_mhmc_step_diag, N, stream,
+                      Key{key0, key1}, chain_offset, step_fold, N, D, step, do_next, eps, eps_per_chain, imm,
+                      imm_stride, divergence_threshold, logp0, ke0, q, p, g, logp_new, weight, sum_log_p_accept, any_divergent,
+                      ever_accepted, prop_q, prop_p, prop_g, prop_logp, prop_energy, n_steps, kick_c, drift_c);
   return bjx_check_launch(what);
 }
 
@@ -1109,10 +1062,9 @@ static int mhmc_finish(const char* what, void* stream, int64_t N, int64_t D, int
                     sum_log_p_accept && prop_q && prop_p && prop_g && prop_logp && prop_energy &&
                     acceptance_rate_out,
                 "bjx_mhmc_finish: bad arguments");
-  hipLaunchKernelGGL(k_mhmc_finish, dim3(bjx_row_grid(N, kWavesPerBlock)), dim3(kBlock), 0,
-                     (hipStream_t)stream, N, D, (float)num_integration_steps, q0, p0, g0, logp0, ke0,
-                     ever_accepted, sum_log_p_accept, prop_q, prop_p, prop_g, prop_logp, prop_energy,
-                     acceptance_rate_out, n_steps);
+  BJX_LAUNCH_ROWS(k_mhmc_finish, N, stream, N, D, (float)num_integration_steps, q0, p0, g0, logp0, ke0,
+                  ever_accepted, sum_log_p_accept, prop_q, prop_p, prop_g, prop_logp, prop_energy,
+                  acceptance_rate_out, n_steps);
   return bjx_check_launch(what);
 }
 

@@ -36,6 +36,18 @@ static inline bool bjx_vec4_ok(int64_t D, P... ptrs) {
   return (D % 4 == 0) && (bjx_vec4_ptr_ok((const void*)ptrs) && ...);
 }
 
+// Launch of a row-per-wave kernel over ROWS rows with the grid and block of that mapping (bjx_rows.h, which the
+// translation unit includes), no shared memory; the kernel's arguments follow.
+#define BJX_LAUNCH_ROWS(KERNEL, ROWS, STREAM, ...)                                                \
+  hipLaunchKernelGGL(KERNEL, dim3(bjx_row_grid(ROWS, bjx::kWavesPerBlock)), dim3(bjx::kBlock), 0, \
+                     (hipStream_t)(STREAM), __VA_ARGS__)
+// The same for a kernel template over the sweep width: KERNEL<4> when VEC4_OK (a bjx_vec4_ok result), else KERNEL<1>.
+#define BJX_LAUNCH_ROWS_VEC(VEC4_OK, KERNEL, ROWS, STREAM, ...)          \
+  do {                                                                   \
+    if (VEC4_OK) BJX_LAUNCH_ROWS(KERNEL<4>, ROWS, STREAM, __VA_ARGS__);  \
+    else BJX_LAUNCH_ROWS(KERNEL<1>, ROWS, STREAM, __VA_ARGS__);          \
+  } while (0)
+
 // Store policy of the cache-resident HMC loop kernels (flat leapfrog, gradient-only Gaussian callable): p, q and g
 // written through L2 (st4_wt, bjx_device.h).  BJX_LF_POLICY=0 gives plain stores (A/B: tools/README.md); read
 // once per process.

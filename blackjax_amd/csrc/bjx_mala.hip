@@ -4,41 +4,18 @@
 // mcmc/diffusions.py::overdamped_langevin, mcmc/proposal.py::compute_asymmetric_acceptance_ratio,
 // static_binomial_sampling, safe_energy_diff.
 //
-// Same layout and mapping as bjx_ghmc.hip: (N, D) row-major fp32, one wavefront owns one chain row at a
-// time, lanes sweep the row in 16-byte pieces (4-byte sweeps when D % 4 != 0 or a pointer is not 16-byte
-// aligned).  A transition is propose -> user callable -> finish: 12 + 8 + 24 = 44 bytes per element.
+// Layout and mapping: bjx_rows.h.  A transition is propose -> user callable -> finish: 12 + 8 + 24 = 44 bytes
+// per element.
 #include <math.h>
 
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 
 using namespace bjx;
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
-
-__device__ __forceinline__ int64_t wave_row0() {
-  return (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-}
-__device__ __forceinline__ int64_t wave_row_stride() { return (int64_t)gridDim.x * kWavesPerBlock; }
-
-template <int VEC>
-__device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const F4 t = ld4(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) st4(p, F4{v[0], v[1], v[2], v[3]});
-  else p[0] = v[0];
-}
 
 // diffusions.py::overdamped_langevin (one_step): q1 = q0 + tau * g0 + sqrt(2 tau) * normal(key_integrator, (D,)),
 // left to right, each `x + s * y` one fmaf.  key_integrator = split(chain key, 2)[0] (mala.py kernel).
@@ -60,14 +37,7 @@ k_mala_propose(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, float t
       float qq[VEC], gg[VEC], z[VEC], qn[VEC];
       ldv<VEC>(q0 + base + j, qq);
       ldv<VEC>(g0 + base + j, gg);
-      if constexpr (VEC == 4) {
-        uint32_t bits[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) bits[e] = key_bits32(kn, (uint64_t)(j + e));
-        normal4_from_bits(bits, z);
-      } else {
-        z[0] = normal_from_bits(key_bits32(kn, (uint64_t)j));
-      }
+      normalv<VEC>(kn, j, z);
 #pragma unroll
       for (int e = 0; e < VEC; ++e) qn[e] = fmaf(s, z[e], fmaf(tau, gg[e], qq[e]));
       stv<VEC>(q1_out + base + j, qn);
@@ -77,21 +47,14 @@ k_mala_propose(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, float t
 
 // The per-chain scalar tail of a transition, from the two fp64 sums of squares (every lane computes it; lane 0
 // writes).  mala.py transition_energy: -logp(new) + 0.25 * (1 / tau) * sum theta^2 with
-// theta = state.position - new.position - tau * new.grad; proposal.py::compute_asymmetric_acceptance_ratio
-// on safe_energy_diff(E(new, state), E(state, new)); static_binomial_sampling -- the draw and compare of
-// k_hmc_finish_diag with key_rmh = split(chain key, 2)[1].
+// theta = state.position - new.position - tau * new.grad; metropolis_accept on
+// safe_energy_diff(E(new, state), E(state, new)), key_rmh = split(chain key, 2)[1].
 __device__ __forceinline__ bool mala_accept(Key key, int64_t gidx, int64_t fold, float tau, double sum_new,
                                             double sum_prev, float lp0, float lp1, float* p_acc_out) {
   const float c = 0.25f * (1.0f / tau);  // two fp32 roundings, as written in mala.py
   const float e_new = fmaf(c, (float)sum_new, -lp1);    // transition_energy(state, new_state)
   const float e_prev = fmaf(c, (float)sum_prev, -lp0);  // transition_energy(new_state, state)
-  float delta = e_prev - e_new;
-  if (delta != delta) delta = -__builtin_inff();  // safe_energy_diff
-  const float p_acc = fminf(exp_cr(delta), 1.0f);
-  const Key kc = chain_key(key, (uint64_t)gidx, fold);
-  const float u = key_uniform(key_child(kc, 1));
-  *p_acc_out = p_acc;
-  return u < p_acc;
+  return metropolis_accept(key, gidx, fold, safe_energy_diff(e_prev - e_new), p_acc_out);
 }
 
 // General two-pass finish.  Pass 1 sweeps q0, q1, g0, g1 once and accumulates both sums of squares; pass 2
@@ -219,14 +182,8 @@ int bjx_mala_propose(void* stream, uint32_t key0, uint32_t key1, int64_t chain_o
   BJX_CHECK_ARG(N >= 0 && D > 0, "bjx_mala_propose: bad sizes");
   if (N == 0) return 0;
   BJX_CHECK_ARG(q0 && g0 && q1_out, "bjx_mala_propose: null pointer");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-  if (bjx_vec4_ok(D, q0, g0, q1_out))
-    hipLaunchKernelGGL(k_mala_propose<4>, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N, D,
-                       tau, tau_per_chain, q0, g0, q1_out);
-  else
-    hipLaunchKernelGGL(k_mala_propose<1>, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N, D,
-                       tau, tau_per_chain, q0, g0, q1_out);
+  BJX_LAUNCH_ROWS_VEC(bjx_vec4_ok(D, q0, g0, q1_out), k_mala_propose, N, stream, Key{key0, key1}, chain_offset,
+                      step_fold, N, D, tau, tau_per_chain, q0, g0, q1_out);
   return bjx_check_launch("bjx_mala_propose");
 }
 
@@ -240,12 +197,9 @@ int bjx_mala_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_of
   BJX_CHECK_ARG(q0 && logp0 && g0 && q1 && logp1 && g1 && q_out && logp_out && g_out && acceptance_rate_out &&
                     is_accepted_out,
                 "bjx_mala_finish: null pointer");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-#define BJX_MALA_FINISH(KERNEL)                                                                               \
-  hipLaunchKernelGGL(KERNEL, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N, D, tau,    \
-                     tau_per_chain, q0, logp0, g0, q1, logp1, g1, q_out, logp_out, g_out, acceptance_rate_out, \
-                     is_accepted_out)
+#define BJX_MALA_FINISH(KERNEL)                                                                                 \
+  BJX_LAUNCH_ROWS(KERNEL, N, stream, Key{key0, key1}, chain_offset, step_fold, N, D, tau, tau_per_chain, q0, logp0, \
+                  g0, q1, logp1, g1, q_out, logp_out, g_out, acceptance_rate_out, is_accepted_out)
   if (bjx_vec4_ok(D, q0, g0, q1, g1, q_out, g_out)) {
     if (D <= 256) BJX_MALA_FINISH(k_mala_finish_res<1>);
     else if (D <= 512) BJX_MALA_FINISH(k_mala_finish_res<2>);

@@ -21,6 +21,7 @@
 #include "bjx_device.h"
 #include "../../include/bjx_nuts.h"
 #endif
+#include "bjx_rows.h"
 #include "bjx_targets_dev.h"
 
 using namespace bjx;
@@ -28,17 +29,6 @@ using namespace bjx;
 
 namespace {
 
-
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
-
-// The wave's index is the same in all 64 lanes: readfirstlane tells the compiler so, which puts
-// everything derived from it (chain index, slot-table addresses, the threefry key arithmetic of the
-// chain's RNG stream) on the scalar unit instead of repeating it in 64 vector lanes.
-__device__ __forceinline__ int64_t wave_row0() {
-  return (int64_t)blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-}
-__device__ __forceinline__ int64_t wave_row_stride() { return (int64_t)gridDim.x * kWavesPerBlock; }
 
 #define FS(slot, c) nt.fs[(int64_t)(slot)*nt.N + (c)]
 #define IS(slot, c) nt.is[(int64_t)(slot)*nt.N + (c)]

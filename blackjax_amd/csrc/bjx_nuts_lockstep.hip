@@ -8,7 +8,7 @@ namespace {
 template <int VEC, bool DENSE>
 __global__ void __launch_bounds__(kBlock)
 k_nuts_init(bjx_nuts_t nt, const float* __restrict__ logp0, const float* __restrict__ ke0) {
-  for (int64_t c = wave_row0(); c < nt.N; c += wave_row_stride())
+  for (int64_t c = wave_row0_uniform(); c < nt.N; c += wave_row_stride())
     nuts_init_chain<VEC, DENSE>(nt, c, logp0[c], ke0[c]);
 }
 
@@ -23,7 +23,7 @@ k_nuts_pre(bjx_nuts_t nt, int32_t depth_arg, int32_t s_arg, int64_t n_rows_arg,
   const StepCtx cx = make_ctx(nt, depth_arg, s_arg, n_rows_arg, ctl);
   const int32_t depth = cx.depth, s = cx.s;
   const int64_t n_rows = cx.n_rows;
-  for (int64_t b = wave_row0(); b < n_rows; b += wave_row_stride()) {
+  for (int64_t b = wave_row0_uniform(); b < n_rows; b += wave_row_stride()) {
     const int64_t c = idx ? (int64_t)idx[b] : b;
     if (!IS(BJX_NUTS_I_ACTIVE, c)) continue;
     int dir;
@@ -50,7 +50,7 @@ k_nuts_mid(bjx_nuts_t nt, int64_t n_rows_arg, const int32_t* __restrict__ idx,
            const int64_t* __restrict__ ctl, float* __restrict__ qf, const float* __restrict__ gf, float kick,
            float drift) {
   const int64_t n_rows = ctl ? (ctl[2] < n_rows_arg ? ctl[2] : n_rows_arg) : n_rows_arg;
-  for (int64_t b = wave_row0(); b < n_rows; b += wave_row_stride()) {
+  for (int64_t b = wave_row0_uniform(); b < n_rows; b += wave_row_stride()) {
     const int64_t c = idx ? (int64_t)idx[b] : b;
     if (!IS(BJX_NUTS_I_ACTIVE, c) || !IS(BJX_NUTS_I_SUB_ACTIVE, c)) continue;
     const int dir = IS(BJX_NUTS_I_DIR, c);
@@ -68,7 +68,7 @@ k_nuts_dense_kick(bjx_nuts_t nt, int32_t depth_arg, int32_t s_arg, int64_t n_row
                   const int32_t* __restrict__ idx, const int64_t* __restrict__ ctl,
                   const float* __restrict__ gf, float kick, float* __restrict__ pc) {
   const StepCtx cx = make_ctx(nt, depth_arg, s_arg, n_rows_arg, ctl);
-  for (int64_t b = wave_row0(); b < cx.n_rows; b += wave_row_stride()) {
+  for (int64_t b = wave_row0_uniform(); b < cx.n_rows; b += wave_row_stride()) {
     const int64_t c = idx ? (int64_t)idx[b] : b;
     float* out = pc + b * nt.D;
     bool act = IS(BJX_NUTS_I_ACTIVE, c) != 0;
@@ -111,7 +111,7 @@ k_nuts_post(bjx_nuts_t nt, int32_t depth_arg, int32_t s_arg, int64_t n_rows_arg,
   const StepCtx cx = make_ctx(nt, depth_arg, s_arg, n_rows_arg, ctl);
   const int32_t depth = cx.depth, s = cx.s;
   const int64_t n_rows = cx.n_rows;
-  for (int64_t b = wave_row0(); b < n_rows; b += wave_row_stride()) {
+  for (int64_t b = wave_row0_uniform(); b < n_rows; b += wave_row_stride()) {
     const int64_t c = idx ? (int64_t)idx[b] : b;
     if (!IS(BJX_NUTS_I_ACTIVE, c) || !IS(BJX_NUTS_I_SUB_ACTIVE, c)) continue;
     nuts_post_chain<VEC, DENSE>(nt, cx, c, b, depth, s, qf, logp_f, gf, fuse_next != 0);
@@ -127,7 +127,7 @@ k_nuts_post_res(bjx_nuts_t nt, int32_t depth_arg, int32_t s_arg, int64_t n_rows_
   const StepCtx cx = make_ctx(nt, depth_arg, s_arg, n_rows_arg, ctl);
   const int32_t depth = cx.depth, s = cx.s;
   const int64_t n_rows = cx.n_rows;
-  for (int64_t b = wave_row0(); b < n_rows; b += wave_row_stride()) {
+  for (int64_t b = wave_row0_uniform(); b < n_rows; b += wave_row_stride()) {
     const int64_t c = idx ? (int64_t)idx[b] : b;
     if (!IS(BJX_NUTS_I_ACTIVE, c) || !IS(BJX_NUTS_I_SUB_ACTIVE, c)) continue;
     nuts_post_chain_resident<4, NI>(nt, cx, c, b, depth, s, qf, logp_f, gf, fuse_next != 0);
@@ -139,7 +139,7 @@ template <int VEC, bool DENSE>
 __global__ void __launch_bounds__(kBlock)
 k_nuts_merge(bjx_nuts_t nt, int32_t depth, int64_t n_rows, const int32_t* __restrict__ idx) {
   const StepCtx kcx{depth, 0, n_rows, Key{nt.key0, nt.key1}, nt.chain_offset, nt.step_fold};
-  for (int64_t b = wave_row0(); b < n_rows; b += wave_row_stride()) {
+  for (int64_t b = wave_row0_uniform(); b < n_rows; b += wave_row_stride()) {
     const int64_t c = idx ? (int64_t)idx[b] : b;
     if (!IS(BJX_NUTS_I_ACTIVE, c)) continue;
     nuts_merge_chain<VEC, DENSE>(nt, kcx, c, depth);

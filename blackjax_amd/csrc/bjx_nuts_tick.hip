@@ -269,7 +269,7 @@ k_nuts_gemm_start(bjx_nuts_t nt, bjx_nuts_async_t ax, int32_t cap) {
   const int lane = threadIdx.x & 63;
   int64_t n = (int64_t)__builtin_amdgcn_readfirstlane(*ax.end_count);
   if (n > cap) n = cap;
-  for (int64_t e = wave_row0(); e < n; e += wave_row_stride()) {
+  for (int64_t e = wave_row0_uniform(); e < n; e += wave_row_stride()) {
     const int64_t c = (int64_t)__builtin_amdgcn_readfirstlane(ax.end_list[e]);
     const int64_t base = c * nt.D;
     const float* pm = ax.gemm_pm + e * nt.D;
@@ -351,7 +351,7 @@ k_nuts_async_gather(int64_t D, const int32_t* __restrict__ n_rows, const int32_t
                     const float* __restrict__ qf_in, float* __restrict__ qf_out) {
   const int lane = threadIdx.x & 63;
   const int64_t n = *n_rows;
-  for (int64_t b = wave_row0(); b < n; b += wave_row_stride()) {
+  for (int64_t b = wave_row0_uniform(); b < n; b += wave_row_stride()) {
     const float* s = qf_in + (int64_t)src[b] * D;
     float* d = qf_out + b * D;
     for (int64_t j = lane; j < D; j += 64) d[j] = s[j];

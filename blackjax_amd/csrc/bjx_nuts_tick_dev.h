@@ -55,7 +55,7 @@ __device__ __forceinline__ int64_t async_n_rows(const bjx_nuts_async_t& ax) {
 template <class F>
 __device__ __forceinline__ void async_for_each_chain(const bjx_nuts_async_t& ax, int want_a, int want_b, F f) {
   const int64_t n_rows = async_n_rows(ax);
-  for (int64_t b = wave_row0(); b < n_rows; b += wave_row_stride()) {
+  for (int64_t b = wave_row0_uniform(); b < n_rows; b += wave_row_stride()) {
     const int chain = ax.rows ? ax.rows[b] : (int)b;
     const int ph = ax.phase[chain];
     if (ph == want_a || ph == want_b)

@@ -16,6 +16,7 @@
 #include "../../include/bjx_pool.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 
 using namespace bjx;
 
@@ -52,16 +53,6 @@ ColGeom col_geom(int64_t N, int64_t D, int vec) {
   return g;
 }
 
-template <int VEC>
-__device__ __forceinline__ void ld_vec(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    F4 t = ld4(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-
 struct OpChees {  // chees_adaptation.py:241-246, 384-386
   static constexpr int K = 4;
   const float* qp;
@@ -74,8 +65,8 @@ struct OpChees {  // chees_adaptation.py:241-246, 384-386
   template <int VEC>
   __device__ __forceinline__ void load(int64_t r, int64_t off, Regs<VEC>& g) const {
     g.w = w[r];
-    ld_vec<VEC>(qp + off, g.x);
-    ld_vec<VEC>(qi + off, g.y);
+    ldv<VEC>(qp + off, g.x);
+    ldv<VEC>(qi + off, g.y);
   }
   template <int VEC>
   __device__ __forceinline__ void acc(const Regs<VEC>& g, double (&a)[K][VEC], const float*) const {
@@ -102,7 +93,7 @@ struct OpSum {  // metric_buffers.py:429
   };
   template <int VEC>
   __device__ __forceinline__ void load(int64_t, int64_t off, Regs<VEC>& g) const {
-    ld_vec<VEC>(x + off, g.t);
+    ldv<VEC>(x + off, g.t);
   }
   template <int VEC>
   __device__ __forceinline__ void acc(const Regs<VEC>& g, double (&a)[K][VEC], const float*) const {
@@ -122,7 +113,7 @@ struct OpCenteredSq {  // metric_buffers.py:430-433
   };
   template <int VEC>
   __device__ __forceinline__ void load(int64_t, int64_t off, Regs<VEC>& g) const {
-    ld_vec<VEC>(x + off, g.t);
+    ldv<VEC>(x + off, g.t);
   }
   template <int VEC>
   __device__ __forceinline__ void acc(const Regs<VEC>& g, double (&a)[K][VEC], const float* c) const {
@@ -150,7 +141,7 @@ __global__ __launch_bounds__(256) void k_colreduce(int64_t N, int64_t D, int tpr
     for (int v = 0; v < VEC; ++v) a[k][v] = 0.0;
   if (c0 < D) {
     float c[VEC] = {};
-    if constexpr (std::is_same<Op, OpCenteredSq>::value) ld_vec<VEC>(op.center + c0, c);
+    if constexpr (std::is_same<Op, OpCenteredSq>::value) ldv<VEC>(op.center + c0, c);
     // U rows are loaded before any is accumulated (memory-level parallelism: U independent 16-byte
     // loads per input in flight per lane); a thread accumulates its rows in ascending order.
     constexpr int U = kColU;
@@ -279,8 +270,8 @@ __device__ __forceinline__ void wcol_load(const WcolGeom<VEC, U>& g, int64_t rb,
     r = r < g.r_hi ? r : g.r_hi - 1;
     an[u] = acc[r];
     dn[u] = is_div[r];
-    ld_vec<VEC>(qp + r * g.D + g.cl, x[u]);
-    ld_vec<VEC>(qi + r * g.D + g.cl, y[u]);
+    ldv<VEC>(qp + r * g.D + g.cl, x[u]);
+    ldv<VEC>(qi + r * g.D + g.cl, y[u]);
   }
 }
 
@@ -542,7 +533,7 @@ __global__ __launch_bounds__(256) void k_chees_weights(int64_t N, int64_t D, con
 #pragma unroll
       for (int r = 0; r < RW; ++r) {
         if (n0 + r < N) {
-          ld_vec<VEC>(qp + (n0 + r) * D + c, x[r]);
+          ldv<VEC>(qp + (n0 + r) * D + c, x[r]);
         } else {
 #pragma unroll
           for (int v = 0; v < VEC; ++v) x[r][v] = 0.0f;
@@ -579,7 +570,7 @@ __global__ __launch_bounds__(256) void k_chees_weights_short(int64_t N, int64_t 
     if (valid)
       for (int64_t c = (int64_t)gl * 4; c < D; c += G * 4) {
         float x[4];
-        ld_vec<4>(qp + n * D + c, x);
+        ldv<4>(qp + n * D + c, x);
         bad |= !(isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]) && isfinite(x[3]));
       }
 #pragma unroll
@@ -672,15 +663,15 @@ __global__ __launch_bounds__(256) void k_chees_criterion(
     double s_pp = 0.0, s_ii = 0.0, s_pv = 0.0;
     for (int64_t c = (int64_t)gl * VEC; c < D; c += G * VEC) {
       float a[VEC], b[VEC], m[VEC], ma[VEC], mb[VEC];
-      ld_vec<VEC>(qp + base + c, a);
-      ld_vec<VEC>(qi + base + c, b);
-      ld_vec<VEC>(pp + base + c, m);
-      ld_vec<VEC>(pm + c, ma);
-      ld_vec<VEC>(im + c, mb);
+      ldv<VEC>(qp + base + c, a);
+      ldv<VEC>(qi + base + c, b);
+      ldv<VEC>(pp + base + c, m);
+      ldv<VEC>(pm + c, ma);
+      ldv<VEC>(im + c, mb);
       float sg[VEC], sq[VEC];
       if constexpr (WHITEN) {
-        ld_vec<VEC>(imm + c, sg);
-        ld_vec<VEC>(isq + c, sq);
+        ldv<VEC>(imm + c, sg);
+        ldv<VEC>(isq + c, sq);
       }
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
@@ -802,8 +793,8 @@ __global__ __launch_bounds__(256) void k_pool_center(int64_t N, int64_t D, const
        i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = i / per_row, c = (i - r * per_row) * VEC;
     float t[VEC], m[VEC];
-    ld_vec<VEC>(x + r * D + c, t);
-    ld_vec<VEC>(center + c, m);
+    ldv<VEC>(x + r * D + c, t);
+    ldv<VEC>(center + c, m);
     if constexpr (VEC == 4) {
       st4(out + r * D + c, F4{t[0] - m[0], t[1] - m[1], t[2] - m[2], t[3] - m[3]});
     } else {

@@ -5,57 +5,22 @@
 // rmh_proposal), blackjax/mcmc/irmh.py (build_kernel), blackjax/util.py::generate_gaussian_noise,
 // mcmc/proposal.py::compute_asymmetric_acceptance_ratio, static_binomial_sampling, safe_energy_diff.
 //
-// Same layout and mapping as bjx_mala.hip: (N, D) row-major fp32, one wavefront owns one chain row at a time, lanes
-// sweep the row in 16-byte pieces (4-byte sweeps when D % 4 != 0 or a pointer is not 16-byte aligned).  A transition
-// is propose -> user callable (value only) -> finish: 8 + 4 + 8 = 20 bytes per element, no gradient anywhere.
+// Layout and mapping: bjx_rows.h.  A transition is propose -> user callable (value only) -> finish:
+// 8 + 4 + 8 = 20 bytes per element, no gradient anywhere.
 #include <math.h>
 
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 
 using namespace bjx;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
-
-__device__ __forceinline__ int64_t wave_row0() {
-  return (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-}
-__device__ __forceinline__ int64_t wave_row_stride() { return (int64_t)gridDim.x * kWavesPerBlock; }
-
-template <int VEC>
-__device__ __forceinline__ void ldv(const float* p, float (&v)[VEC]) {
-  if constexpr (VEC == 4) {
-    const F4 t = ld4(p);
-    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-  } else {
-    v[0] = p[0];
-  }
-}
-template <int VEC>
-__device__ __forceinline__ void stv(float* p, const float (&v)[VEC]) {
-  if constexpr (VEC == 4) st4(p, F4{v[0], v[1], v[2], v[3]});
-  else p[0] = v[0];
-}
-
-// normal(key, (D,))[j .. j + VEC)
-template <int VEC>
-__device__ __forceinline__ void normalv(Key kn, int64_t j, float (&z)[VEC]) {
-  if constexpr (VEC == 4) {
-    uint32_t bits[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) bits[e] = key_bits32(kn, (uint64_t)(j + e));
-    normal4_from_bits(bits, z);
-  } else {
-    z[0] = normal_from_bits(key_bits32(kn, (uint64_t)j));
-  }
-}
-
-// The two keys of a transition: key_proposal, key_accept = split(chain key, 2) (random_walk.py, irmh.py kernel).
-enum { kKeyProposal = 0, kKeyAccept = 1 };
+// The two keys of a transition: key_proposal, key_accept = split(chain key, 2) (random_walk.py, irmh.py kernel);
+// metropolis_accept draws from the second.
+enum { kKeyProposal = 0 };
 
 // out[r] = normal(k_r, (D,)) with k_r the chain key (child < 0) or its child: a user generator's draw
 // (random.chain_normal) and the left operand of the dense step's product.  4 B written per element.
@@ -124,8 +89,8 @@ k_rw_propose_lin(int64_t N, int64_t D, const float* __restrict__ move_lin, const
   }
 }
 
-// random_walk.py::build_rmh (transition_energy, kernel) with proposal.py::compute_asymmetric_acceptance_ratio on
-// safe_energy_diff and static_binomial_sampling.  f_ip[r] = proposal_logdensity_fn(initial, proposed),
+// random_walk.py::build_rmh (transition_energy, kernel) with metropolis_accept on safe_energy_diff.
+// f_ip[r] = proposal_logdensity_fn(initial, proposed),
 // f_pi[r] = proposal_logdensity_fn(proposed, initial); both null for a symmetric proposal.  Every lane computes the
 // row's scalars, lane 0 writes them; the select then reads ONLY the chosen source row (the branch is wave-uniform)
 // and writes it out of place: 4 B read + 4 B written per element.
@@ -143,11 +108,8 @@ k_rw_finish(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, const floa
       e_init = e_init - f_ip[r];  // transition_energy(initial, proposed)
       e_new = e_new - f_pi[r];    // transition_energy(proposed, initial)
     }
-    float delta = e_init - e_new;
-    if (delta != delta) delta = -__builtin_inff();  // safe_energy_diff
-    const float p_acc = fminf(exp_cr(delta), 1.0f);
-    const Key kc = chain_key(key, (uint64_t)(r + off), fold);
-    const bool accept = key_uniform(key_child(kc, kKeyAccept)) < p_acc;
+    float p_acc;
+    const bool accept = metropolis_accept(key, r + off, fold, safe_energy_diff(e_init - e_new), &p_acc);
     if (lane == 0) {
       acc_rate_out[r] = p_acc;
       is_acc_out[r] = accept ? 1 : 0;
@@ -172,14 +134,8 @@ int bjx_rw_noise(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offse
   BJX_CHECK_ARG(N >= 0 && D > 0 && child >= -1 && child <= 1, "bjx_rw_noise: bad sizes");
   if (N == 0) return 0;
   BJX_CHECK_ARG(out, "bjx_rw_noise: null pointer");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-  if (bjx_vec4_ok(D, out))
-    hipLaunchKernelGGL(k_rw_noise<4>, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, (int)child,
-                       N, D, out);
-  else
-    hipLaunchKernelGGL(k_rw_noise<1>, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, (int)child,
-                       N, D, out);
+  BJX_LAUNCH_ROWS_VEC(bjx_vec4_ok(D, out), k_rw_noise, N, stream, Key{key0, key1}, chain_offset, step_fold,
+                      (int)child, N, D, out);
   return bjx_check_launch("bjx_rw_noise");
 }
 
@@ -191,21 +147,12 @@ int bjx_rw_propose(void* stream, uint32_t key0, uint32_t key1, int64_t chain_off
   BJX_CHECK_ARG(q0 && q1_out, "bjx_rw_propose: null pointer");
   BJX_CHECK_ARG(!(sigma_diag && move_lin), "bjx_rw_propose: sigma_diag and move_lin are exclusive");
   BJX_CHECK_ARG(q0 != q1_out, "bjx_rw_propose: out of place only");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const hipStream_t s = (hipStream_t)stream;
-  const Key key{key0, key1};
   const bool v4 = bjx_vec4_ok(D, sigma_diag, move_lin, q0, q1_out);
-  if (move_lin) {
-    if (v4) hipLaunchKernelGGL(k_rw_propose_lin<4>, grid, block, 0, s, N, D, move_lin, q0, q1_out);
-    else hipLaunchKernelGGL(k_rw_propose_lin<1>, grid, block, 0, s, N, D, move_lin, q0, q1_out);
-  } else {
-    if (v4)
-      hipLaunchKernelGGL(k_rw_propose<4>, grid, block, 0, s, key, chain_offset, step_fold, N, D, sigma, sigma_diag, q0,
-                         q1_out);
-    else
-      hipLaunchKernelGGL(k_rw_propose<1>, grid, block, 0, s, key, chain_offset, step_fold, N, D, sigma, sigma_diag, q0,
-                         q1_out);
-  }
+  if (move_lin)
+    BJX_LAUNCH_ROWS_VEC(v4, k_rw_propose_lin, N, stream, N, D, move_lin, q0, q1_out);
+  else
+    BJX_LAUNCH_ROWS_VEC(v4, k_rw_propose, N, stream, Key{key0, key1}, chain_offset, step_fold, N, D, sigma,
+                        sigma_diag, q0, q1_out);
   return bjx_check_launch("bjx_rw_propose");
 }
 
@@ -221,16 +168,9 @@ int bjx_rw_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offs
                 "bjx_rw_finish: f_init_prop and f_prop_init go together");
   BJX_CHECK_ARG(q_out != q0 && q_out != q1 && logp_out != logp0 && logp_out != logp1,
                 "bjx_rw_finish: out of place only");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  const Key key{key0, key1};
-  if (bjx_vec4_ok(D, q0, q1, q_out))
-    hipLaunchKernelGGL(k_rw_finish<4>, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N, D, q0,
-                       logp0, q1, logp1, f_init_prop, f_prop_init, q_out, logp_out, acceptance_rate_out,
-                       is_accepted_out);
-  else
-    hipLaunchKernelGGL(k_rw_finish<1>, grid, block, 0, (hipStream_t)stream, key, chain_offset, step_fold, N, D, q0,
-                       logp0, q1, logp1, f_init_prop, f_prop_init, q_out, logp_out, acceptance_rate_out,
-                       is_accepted_out);
+  BJX_LAUNCH_ROWS_VEC(bjx_vec4_ok(D, q0, q1, q_out), k_rw_finish, N, stream, Key{key0, key1}, chain_offset,
+                      step_fold, N, D, q0, logp0, q1, logp1, f_init_prop, f_prop_init, q_out, logp_out,
+                      acceptance_rate_out, is_accepted_out);
   return bjx_check_launch("bjx_rw_finish");
 }
 

@@ -14,13 +14,12 @@
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 
 using namespace bjx;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
 constexpr int kScanItems = 4;                    // consecutive items per thread
 constexpr int kScanTile = kBlock * kScanItems;   // 1024 items per workgroup
 constexpr int kRedBlock = 1024;                  // the one workgroup of the reweight / ESS kernels
@@ -380,11 +379,7 @@ int bjx_smc_gather(void* stream, int64_t N, int64_t num_samples, int64_t D, cons
   if (num_samples == 0) return 0;
   BJX_CHECK_ARG(x && ancestors && out, "bjx_smc_gather: null pointer");
   BJX_CHECK_ARG(x != out, "bjx_smc_gather: out of place only");
-  const dim3 grid(bjx_row_grid(num_samples, kWavesPerBlock)), block(kBlock);
-  if (bjx_vec4_ok(D, x, out))
-    hipLaunchKernelGGL(k_gather<4>, grid, block, 0, (hipStream_t)stream, N, num_samples, D, x, ancestors, out);
-  else
-    hipLaunchKernelGGL(k_gather<1>, grid, block, 0, (hipStream_t)stream, N, num_samples, D, x, ancestors, out);
+  BJX_LAUNCH_ROWS_VEC(bjx_vec4_ok(D, x, out), k_gather, num_samples, stream, N, num_samples, D, x, ancestors, out);
   return bjx_check_launch("bjx_smc_gather");
 }
 

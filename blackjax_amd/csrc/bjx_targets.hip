@@ -5,19 +5,12 @@
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 #include "bjx_targets_dev.h"
 
 using namespace bjx;
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
-
-__device__ __forceinline__ int64_t wave_row0() {
-  return (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
-}
-__device__ __forceinline__ int64_t wave_row_stride() { return (int64_t)gridDim.x * kWavesPerBlock; }
 
 // g = -(q*inv_var) ; logp = 0.5 * sum q*g
 template <int VEC, bool NT = false>
@@ -255,33 +248,22 @@ int bjx_target_diag_gaussian(void* stream, int64_t N, int64_t D, const float* in
   BJX_CHECK_ARG(N >= 0 && D > 0, "bjx_target_diag_gaussian: bad arguments");
   if (N == 0) return 0;  // an empty batch has no buffers to check
   BJX_CHECK_ARG(inv_var && q && logp_out && g_out, "bjx_target_diag_gaussian: bad arguments");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock)), block(kBlock);
-  if (bjx_vec4_ok(D, inv_var, q, g_out) && D <= 16)
-    hipLaunchKernelGGL(k_diag_gaussian_short<4>, dim3(bjx_row_grid((N + 15) / 16, kWavesPerBlock)), block, 0,
-                       (hipStream_t)stream, N, D, inv_var, q, logp_out, g_out);
-  else if (bjx_vec4_ok(D, inv_var, q, g_out) && D <= 32)
-    hipLaunchKernelGGL(k_diag_gaussian_short<8>, dim3(bjx_row_grid((N + 7) / 8, kWavesPerBlock)), block, 0,
-                       (hipStream_t)stream, N, D, inv_var, q, logp_out, g_out);
-  else if (bjx_vec4_ok(D, inv_var, q, g_out) && D <= 64)
-    hipLaunchKernelGGL(k_diag_gaussian_short<16>, dim3(bjx_row_grid((N + 3) / 4, kWavesPerBlock)), block, 0,
-                       (hipStream_t)stream, N, D, inv_var, q, logp_out, g_out);
-  else if (bjx_vec4_ok(D, inv_var, q, g_out) && D <= 128)
-    hipLaunchKernelGGL(k_diag_gaussian_short<32>, dim3(bjx_row_grid((N + 1) / 2, kWavesPerBlock)), block, 0,
-                       (hipStream_t)stream, N, D, inv_var, q, logp_out, g_out);
-  else if (bjx_vec4_ok(D, inv_var, q, g_out)) {
+  const bool v4 = bjx_vec4_ok(D, inv_var, q, g_out);
+#define BJX_DG(KERNEL, ROWS) BJX_LAUNCH_ROWS(KERNEL, ROWS, stream, N, D, inv_var, q, logp_out, g_out)
+  if (v4 && D <= 16) BJX_DG(k_diag_gaussian_short<4>, (N + 15) / 16);
+  else if (v4 && D <= 32) BJX_DG(k_diag_gaussian_short<8>, (N + 7) / 8);
+  else if (v4 && D <= 64) BJX_DG(k_diag_gaussian_short<16>, (N + 3) / 4);
+  else if (v4 && D <= 128) BJX_DG(k_diag_gaussian_short<32>, (N + 1) / 2);
+  else if (v4) {
     // a batch larger than the Infinity Cache streams from HBM: nontemporal q loads / g stores
     // (BJX_LF_NT=0 / 1 forces plain / nontemporal, the switch of the leapfrog kernel)
     static const int nt_mode = [] { const char* e = getenv("BJX_LF_NT"); return e ? atoi(e) : -1; }();
     const bool nt = nt_mode < 0 ? N * D * 8 > ((int64_t)256 << 20) : nt_mode != 0;
-    if (nt)
-      hipLaunchKernelGGL((k_diag_gaussian<4, true>), grid, block, 0, (hipStream_t)stream, N, D, inv_var, q,
-                         logp_out, g_out);
-    else
-      hipLaunchKernelGGL((k_diag_gaussian<4, false>), grid, block, 0, (hipStream_t)stream, N, D, inv_var, q,
-                         logp_out, g_out);
+    if (nt) BJX_DG((k_diag_gaussian<4, true>), N);
+    else BJX_DG((k_diag_gaussian<4, false>), N);
   } else
-    hipLaunchKernelGGL(k_diag_gaussian<1>, grid, block, 0, (hipStream_t)stream, N, D, inv_var, q,
-                       logp_out, g_out);
+    BJX_DG(k_diag_gaussian<1>, N);
+#undef BJX_DG
   return bjx_check_launch("bjx_target_diag_gaussian");
 }
 
@@ -312,8 +294,7 @@ int bjx_target_diag_gaussian_grad(void* stream, int64_t N, int64_t D, const floa
       hipLaunchKernelGGL((k_diag_gaussian_grad_flat_any<false, true>), grid, block, 0, s, total4, D4, inv_var, q, g_out);
     else hipLaunchKernelGGL(k_diag_gaussian_grad_flat_any<false>, grid, block, 0, s, total4, D4, inv_var, q, g_out);
   } else {
-    hipLaunchKernelGGL(k_diag_gaussian_grad_rows, dim3(bjx_row_grid(N, kWavesPerBlock)), block, 0, s, N, D,
-                       inv_var, q, g_out);
+    BJX_LAUNCH_ROWS(k_diag_gaussian_grad_rows, N, stream, N, D, inv_var, q, g_out);
   }
   return bjx_check_launch("bjx_target_diag_gaussian_grad");
 }
@@ -323,7 +304,6 @@ int bjx_target_neal_funnel(void* stream, int64_t N, int64_t D, const float* q, f
   BJX_CHECK_ARG(N >= 0 && D >= 2, "bjx_target_neal_funnel: bad arguments");
   if (N == 0) return 0;
   BJX_CHECK_ARG(q && logp_out && g_out, "bjx_target_neal_funnel: bad arguments");
-  const dim3 grid(bjx_row_grid(N, kWavesPerBlock));
   hipStream_t st = (hipStream_t)stream;
   if (bjx_vec4_ok(D, q, g_out) && D <= 1024) {
     const dim3 wgrid((unsigned)(N < ((int64_t)1 << 20) ? N : ((int64_t)1 << 20)));
@@ -331,7 +311,7 @@ int bjx_target_neal_funnel(void* stream, int64_t N, int64_t D, const float* q, f
     else if (D <= 512) hipLaunchKernelGGL(k_neal_funnel_v4<2>, wgrid, dim3(64), 0, st, N, D, q, logp_out, g_out);
     else hipLaunchKernelGGL(k_neal_funnel_v4<4>, wgrid, dim3(64), 0, st, N, D, q, logp_out, g_out);
   } else {
-    hipLaunchKernelGGL(k_neal_funnel, grid, dim3(kBlock), 0, st, N, D, q, logp_out, g_out);
+    BJX_LAUNCH_ROWS(k_neal_funnel, N, stream, N, D, q, logp_out, g_out);
   }
   return bjx_check_launch("bjx_target_neal_funnel");
 }
@@ -341,8 +321,7 @@ int bjx_target_ar1_gaussian(void* stream, int64_t N, int64_t D, float diag_edge,
   BJX_CHECK_ARG(N >= 0 && D >= 2, "bjx_target_ar1_gaussian: bad arguments");
   if (N == 0) return 0;
   BJX_CHECK_ARG(q && logp_out && g_out, "bjx_target_ar1_gaussian: bad arguments");
-  hipLaunchKernelGGL(k_ar1_gaussian, dim3(bjx_row_grid(N, kWavesPerBlock)), dim3(kBlock), 0,
-                     (hipStream_t)stream, N, D, diag_edge, diag_mid, off, q, logp_out, g_out);
+  BJX_LAUNCH_ROWS(k_ar1_gaussian, N, stream, N, D, diag_edge, diag_mid, off, q, logp_out, g_out);
   return bjx_check_launch("bjx_target_ar1_gaussian");
 }
 

@@ -14,14 +14,12 @@
 #include "../../include/bjx_nuts.h"  // BJX_TARGET_*
 #include "bjx_device.h"
 #include "bjx_host.h"
+#include "bjx_rows.h"
 #include "bjx_traj_dev.h"
 
 using namespace bjx;
 
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / BJX_WAVE;
 
 template <int NI, class Target>
 __global__ void __launch_bounds__(kBlock) k_hmc_trajectory_diag(TrajArgs a) {

@@ -15,6 +15,7 @@
 #pragma once
 
 #include "bjx_device.h"
+#include "bjx_rows.h"
 #include "bjx_targets_dev.h"
 
 namespace bjx {
@@ -171,9 +172,10 @@ __device__ __forceinline__ void hmc_trajectory_rows(const TrajArgs& a) {
     const float lp0 = a.logp0[r];
     const float H0 = -lp0 + ke0;
     const float H1 = -lp1 + ke1;
-    float delta = H0 - H1;
-    if (delta != delta) delta = -__builtin_inff();   // proposal.py:45-48
-    const bool is_div = (-delta) > a.thr;             // hmc.py:162
+    const float delta = safe_energy_diff(H0 - H1);
+    const bool is_div = (-delta) > a.thr;  // hmc.py:162
+    // metropolis_accept (bjx_rows.h) written out: the chain key is already in registers here, and the call changes
+    // the code generated for this kernel
     const float p_acc = fminf(exp_cr(delta), 1.0f);   // proposal.py:225
     const Key ki = key_child(kc, 1);                   // split(kc, 2)[1]
     const float u = key_uniform(ki);
