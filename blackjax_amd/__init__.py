@@ -17,7 +17,7 @@ from . import hmc as _hmc
 from . import irmh as _irmh
 from . import mala as _mala
 from . import nuts as _nuts
-from . import adaptation, chees, diagnostics, distributed, integrators, meads, metrics, optim, random, random_walk, rtc, smc, targets, util
+from . import adaptation, chees, diagnostics, distributed, integrators, meads, metrics, optim, random, random_walk, rtc, sgmcmc, smc, targets, util
 from .adaptation import staged_adaptation, window_adaptation
 from .chees import chees_adaptation
 from .meads import meads_adaptation
@@ -89,5 +89,10 @@ irmh = GenerateSamplingAPI(_irmh.as_top_level_api, _irmh.init, _irmh.build_kerne
 tempered_smc = GenerateSamplingAPI(smc.tempered.as_top_level_api, smc.tempered.init, smc.tempered.build_kernel)
 adaptive_tempered_smc = GenerateSamplingAPI(smc.adaptive_tempered.as_top_level_api, smc.adaptive_tempered.init,
                                             smc.adaptive_tempered.build_kernel)
+# Stochastic-gradient MCMC (blackjax/sgmcmc/sgld.py, sghmc.py, sgnht.py): the gradient is a minibatch estimate from the
+# user's callable, the noise draw + diffusion update (+ thermostat) is one fused launch per step
+sgld = GenerateSamplingAPI(sgmcmc.sgld.as_top_level_api, sgmcmc.sgld.init, sgmcmc.sgld.build_kernel)
+sghmc = GenerateSamplingAPI(sgmcmc.sghmc.as_top_level_api, sgmcmc.sghmc.init, sgmcmc.sghmc.build_kernel)
+sgnht = GenerateSamplingAPI(sgmcmc.sgnht.as_top_level_api, sgmcmc.sgnht.init, sgmcmc.sgnht.build_kernel)
 
-__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "barker", "barker_proposal", "elliptical_slice", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "smc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]
+__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "barker", "barker_proposal", "elliptical_slice", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "smc", "sgld", "sghmc", "sgnht", "sgmcmc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]

@@ -317,6 +317,15 @@ SIGNATURES.update({
     "bjx_rw_propose": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float] + [_f32p] * 4,
     "bjx_rw_finish": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64] + [_f32p] * 9 + [_u8p],
 })
+# include/bjx_hip.h "SGMCMC" (sgld / sghmc / sgnht: one fused launch per step, the normals drawn in registers)
+SIGNATURES.update({
+    "bjx_sgld_step": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, _f32p, c_float,
+                      _f32p] + [_f32p] * 3,
+    "bjx_sghmc_step": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_float,
+                       c_float, _f32p, c_float, _f32p] + [_f32p] * 5,
+    "bjx_sgnht_step": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, c_float,
+                       c_float, _f32p, c_float, _f32p] + [_f32p] * 7,
+})
 INT64_FUNCTIONS = {"bjx_pool_workspace_bytes": [c_int64, c_int64],
                    "bjx_meads_workspace_bytes": [c_int64, c_int64],
                    "bjx_smc_resample_workspace_bytes": [c_int64]}

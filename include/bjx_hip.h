@@ -481,6 +481,39 @@ int bjx_mala_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_of
                     float* q_out, float* logp_out, float* g_out, float* acceptance_rate_out,
                     uint8_t* is_accepted_out);
 
+/* ---- SGMCMC (blackjax.sgld / sghmc / sgnht; blackjax/sgmcmc/) ---------------------------------
+ * Stochastic-gradient samplers: the gradient estimate `g` comes from the caller (a minibatch gradient), a step is
+ * one launch that draws its normals in registers.  `eps` is the step size and `temperature` the temperature, each a
+ * scalar or a device (N,) array (`*_per_chain`, which wins when non-null).  Outputs are out of place: no output may
+ * alias an input.  Keys: k_i = split(key, .)[chain_offset+i] (or its step_fold child), used unsplit for the noise
+ * of SGLD and SGNHT.  Nothing tests for non-finite values.  N == 0 is a no-op.
+ *
+ * SGLD: q1 = q + eps g + sqrtf((2 T) eps) normal(k_i, (D,)), left to right, one fma per term.
+ * Replaces: sgmcmc/diffusions.py::overdamped_langevin (one_step) as called by sgmcmc/sgld.py (kernel). */
+int bjx_sgld_step(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int64_t N,
+                  int64_t D, float eps, const float* eps_per_chain, float temperature,
+                  const float* temperature_per_chain, const float* q, const float* g, float* q_out);
+/* SGHMC, integration step `step_index` = l of L (one launch per step; the caller evaluates g_l at q_l between):
+ *   q_{l+1} = q_l + eps p_l
+ *   p_{l+1} = (1 - alpha eps) p_l + eps g_l + s normal(split(k_i, L)[l], (D,)),  s = sqrtf((eps T)(2 alpha - eps beta))
+ * with c = 1 - alpha eps two fp32 roundings, c p_l one rounding, then one fma per term.
+ *   p_in == NULL: p_l is the momentum refresh normal(k_i, (D,)), drawn in registers (l = 0).
+ *   g == NULL and p_out == NULL: only q_{l+1} is written and no noise is drawn (l = L - 1; the sampler drops the
+ *   final momentum).  g and p_out must be null together.  Both forms at once serve L = 1.
+ * Replaces: sgmcmc/sghmc.py (kernel: momentum refresh, integration loop) ; sgmcmc/diffusions.py::sghmc (one_step). */
+int bjx_sghmc_step(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int64_t N,
+                   int64_t D, int64_t step_index, float alpha, float beta, float eps, const float* eps_per_chain,
+                   float temperature, const float* temperature_per_chain, const float* q, const float* p_in,
+                   const float* g, float* q_out, float* p_out);
+/* SGNHT, with z = normal(k_i, (D,)) and s as for SGHMC; xi is the (N,) thermostat:
+ *   q1 = q + eps p ; p1 = ((p - (eps xi) p) + eps g) + s z, one fma per term
+ *   xi1 = xi + eps (m - T), m = sum_j p1_j^2 / D accumulated in fp64 and rounded once
+ * Replaces: sgmcmc/diffusions.py::sgnht (one_step) as called by sgmcmc/sgnht.py (kernel). */
+int bjx_sgnht_step(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int64_t N,
+                   int64_t D, float alpha, float beta, float eps, const float* eps_per_chain, float temperature,
+                   const float* temperature_per_chain, const float* q, const float* p, const float* xi,
+                   const float* g, float* q_out, float* p_out, float* xi_out);
+
 /* ---- Barker (blackjax.barker_proposal; blackjax/mcmc/barker.py) ------------------------------
  * One transition = bjx_barker_propose -> user callable at q1 -> bjx_barker_finish.  `tau` as for MALA.  `imm` is a
  * diagonal inverse mass matrix: null = ones, (D,) with imm_row_stride 0, or (N, D) with imm_row_stride D.  Keys:
