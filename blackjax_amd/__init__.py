@@ -16,6 +16,7 @@ from . import ghmc as _ghmc
 from . import hmc as _hmc
 from . import irmh as _irmh
 from . import mala as _mala
+from . import marginal_latent_gaussian
 from . import nuts as _nuts
 from . import adaptation, chees, diagnostics, distributed, integrators, meads, metrics, optim, random, random_walk, rtc, sgmcmc, smc, targets, util
 from .adaptation import staged_adaptation, window_adaptation
@@ -75,6 +76,10 @@ barker_proposal = barker
 # Elliptical slice sampling (blackjax/mcmc/elliptical_slice.py): Gaussian prior, value-only log-likelihood, no gradient
 elliptical_slice = GenerateSamplingAPI(_elliptical_slice.as_top_level_api, _elliptical_slice.init,
                                        _elliptical_slice.build_kernel)
+# Marginal latent-Gaussian sampler (blackjax/mcmc/marginal_latent_gaussian.py): Gaussian prior, log-likelihood with a
+# gradient, proposal preconditioned by the prior covariance; one gradient per transition, no host read
+mgrad_gaussian = GenerateSamplingAPI(marginal_latent_gaussian.as_top_level_api, marginal_latent_gaussian.init,
+                                     marginal_latent_gaussian.build_kernel)
 # Random-walk Metropolis (blackjax/mcmc/random_walk.py, irmh.py): gradient-free, value-only log-density.  rmh takes any
 # batched proposal generator, additive_step_random_walk adds a random step (normal_random_walk: the fused Gaussian
 # step), irmh proposes independently of the position
@@ -95,4 +100,4 @@ sgld = GenerateSamplingAPI(sgmcmc.sgld.as_top_level_api, sgmcmc.sgld.init, sgmcm
 sghmc = GenerateSamplingAPI(sgmcmc.sghmc.as_top_level_api, sgmcmc.sghmc.init, sgmcmc.sghmc.build_kernel)
 sgnht = GenerateSamplingAPI(sgmcmc.sgnht.as_top_level_api, sgmcmc.sgnht.init, sgmcmc.sgnht.build_kernel)
 
-__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "barker", "barker_proposal", "elliptical_slice", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "smc", "sgld", "sghmc", "sgnht", "sgmcmc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]
+__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "barker", "barker_proposal", "elliptical_slice", "mgrad_gaussian", "marginal_latent_gaussian", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "smc", "sgld", "sghmc", "sgnht", "sgmcmc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]

@@ -326,6 +326,15 @@ SIGNATURES.update({
     "bjx_sgnht_step": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, c_float,
                        c_float, _f32p, c_float, _f32p] + [_f32p] * 7,
 })
+# include/bjx_hip.h "marginal latent Gaussian" (mgrad_gaussian: proposal in the prior's eigenbasis, mean shift of the
+# likelihood, accept + select)
+SIGNATURES.update({
+    "bjx_mgrad_propose": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, _f32p]
+                         + [_f32p] * 4,
+    "bjx_mgrad_shift": [c_void_p, c_int64, c_int64] + [_f32p] * 6,
+    "bjx_mgrad_finish": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, _f32p]
+                        + [_f32p] * 17 + [_u8p],
+})
 INT64_FUNCTIONS = {"bjx_pool_workspace_bytes": [c_int64, c_int64],
                    "bjx_meads_workspace_bytes": [c_int64, c_int64],
                    "bjx_smc_resample_workspace_bytes": [c_int64]}

@@ -481,6 +481,45 @@ int bjx_mala_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_of
                     float* q_out, float* logp_out, float* g_out, float* acceptance_rate_out,
                     uint8_t* is_accepted_out);
 
+/* ---- marginal latent Gaussian (blackjax.mgrad_gaussian; blackjax/mcmc/marginal_latent_gaussian.py) ----
+ * Gaussian prior N(0, C), C = U diag(Gamma) U^T shared by all chains, arbitrary log-LIKELIHOOD with a gradient (a
+ * prior mean is folded into the likelihood: bjx_mgrad_shift).  The kernels work on rows in the prior's eigenbasis,
+ * U_x = U^T x and U_grad_x = U^T g; the rotations are the caller's GEMMs.  One transition of a dense prior =
+ *   bjx_mgrad_propose -> bjx_dense_matmul(t, U^T) = y -> user callable at y [-> bjx_mgrad_shift]
+ *   -> bjx_dense_matmul_bt(y, U, U^T) = U_y -> bjx_dense_matmul_bt(g_y, U, U^T) = U_grad_y -> bjx_mgrad_finish
+ * and of a diagonal prior (U = I, Gamma = the variances) propose -> user callable at t [-> shift] -> finish.
+ * `delta` is the step size (scalar, or a device (N,) array `delta_per_chain` as with `eps`); `gamma` is (D,).  Keys:
+ *   k_i = split(key, .)[chain_offset+i] (or its step_fold child) ; y_key, u_key = split(k_i, 2)
+ * Per element, in fp32 left to right with correctly rounded divisions:
+ *   Gamma_1 = Gamma delta / (delta + 2 Gamma) ; Gamma_3 = (delta + 2 Gamma) / (delta + 4 Gamma) ; Gamma_2 = Gamma_1 / Gamma_3
+ * Outputs are out of place: no output may alias an input.  N == 0 is a no-op.
+ *
+ * Proposal: t = Gamma_1 (U_x / (0.5 delta) + U_grad_x) + sqrtf(Gamma_2) normal(y_key, (D,)), the sum one fma.
+ * Replaces: mcmc/marginal_latent_gaussian.py (build_kernel: kernel, up to y = U @ ...). */
+int bjx_mgrad_propose(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold,
+                      int64_t N, int64_t D, float delta, const float* delta_per_chain, const float* gamma,
+                      const float* u_x, const float* u_grad_x, float* t_out);
+/* logp_out = logp + dot(y, shift) (fp64 sum rounded once) ; g_out = g + shift, with shift = C^-1 mean (D,).
+ * Replaces: mcmc/marginal_latent_gaussian.py::generate_mean_shifted_logprob and its gradient. */
+int bjx_mgrad_shift(void* stream, int64_t N, int64_t D, const float* shift, const float* y, const float* logp,
+                    const float* g, float* logp_out, float* g_out);
+/* Metropolis-Hastings accept + state select, out of place:
+ *   t_x = Gamma_1 (U_x / (0.5 delta) + 0.5 U_grad_x) ; t_y = Gamma_1 (U_y / (0.5 delta) + 0.5 U_grad_y)
+ *   hxy = sum (U_x - t_y) (Gamma_3 U_grad_y) ; hyx = sum (U_y - t_x) (Gamma_3 U_grad_x)   (fp64 sums, rounded once)
+ *   log_ratio = ((logp_y - logp_x) + hxy) - hyx (NaN -> -inf) ; p_acc = min(1, exp(log_ratio))
+ *   accept = uniform(u_key) < p_acc ; (x, logp, g, U_x, U_grad_x)_out = accept ? the proposal's : the state's
+ * Dense prior: x, g_x, y, g_y, x_out, g_out are all given.  Diagonal prior: all six are NULL -- position and gradient
+ * ARE u_x / u_grad_x (u_y / u_grad_y for the proposal) and are written once, to u_x_out / u_grad_x_out.
+ * is_accepted_out: one byte per chain, 0 / 1.
+ * Replaces: mcmc/marginal_latent_gaussian.py (build_kernel: kernel, from hxy on) ; mcmc/proposal.py::
+ * static_binomial_sampling, safe_energy_diff. */
+int bjx_mgrad_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int64_t N,
+                     int64_t D, float delta, const float* delta_per_chain, const float* gamma, const float* x,
+                     const float* logp_x, const float* g_x, const float* u_x, const float* u_grad_x, const float* y,
+                     const float* logp_y, const float* g_y, const float* u_y, const float* u_grad_y, float* x_out,
+                     float* logp_out, float* g_out, float* u_x_out, float* u_grad_x_out, float* acceptance_rate_out,
+                     uint8_t* is_accepted_out);
+
 /* ---- SGMCMC (blackjax.sgld / sghmc / sgnht; blackjax/sgmcmc/) ---------------------------------
  * Stochastic-gradient samplers: the gradient estimate `g` comes from the caller (a minibatch gradient), a step is
  * one launch that draws its normals in registers.  `eps` is the step size and `temperature` the temperature, each a
