@@ -317,7 +317,8 @@ SIGNATURES.update({
     "bjx_rw_propose": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float] + [_f32p] * 4,
     "bjx_rw_finish": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64] + [_f32p] * 9 + [_u8p],
 })
-# include/bjx_hip.h "SGMCMC" (sgld / sghmc / sgnht: one fused launch per step, the normals drawn in registers)
+# include/bjx_hip.h "SGMCMC" (sgld / sghmc / sgnht: one fused launch per step, the normals drawn in registers; csgld:
+# the scaled-gradient step and the energy-histogram update)
 SIGNATURES.update({
     "bjx_sgld_step": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, _f32p, c_float,
                       _f32p] + [_f32p] * 3,
@@ -325,6 +326,10 @@ SIGNATURES.update({
                        c_float, _f32p, c_float, _f32p] + [_f32p] * 5,
     "bjx_sgnht_step": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, c_float,
                        c_float, _f32p, c_float, _f32p] + [_f32p] * 7,
+    "bjx_csgld_step": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_int64, c_float, c_float,
+                       c_float, _f32p, c_float, _f32p] + [_f32p] * 3 + [c_void_p, _f32p],
+    "bjx_csgld_update": [c_void_p, c_int64, c_int64, c_float, c_float, c_float, c_float, _f32p] + [_f32p] * 3
+                        + [c_void_p],
 })
 # include/bjx_hip.h "marginal latent Gaussian" (mgrad_gaussian: proposal in the prior's eigenbasis, mean shift of the
 # likelihood, accept + select)

@@ -29,7 +29,7 @@ def _per_chain(value, n_chains: int, device, name: str):
         raise ValueError(str(e).replace("step_size", name)) from None
 
 
-def _batch_args(position, step_size, temperature, name: str = "position"):
+def _batch_args(position, step_size, temperature, name: str = "position", step_size_name: str = "step_size"):
     """-> contiguous device position, (eps, per-chain eps), (T, per-chain T).  Shapes are checked before the device,
     so that a wrong-length per-chain argument is a ``ValueError`` wherever the tensors live."""
     if not isinstance(position, torch.Tensor):
@@ -37,7 +37,7 @@ def _batch_args(position, step_size, temperature, name: str = "position"):
     if position.ndim != 2:
         raise ValueError(f"{name} must be (n_chains, dim), got {tuple(position.shape)}")
     n = position.shape[0]
-    eps = _per_chain(step_size, n, position.device, "step_size")
+    eps = _per_chain(step_size, n, position.device, step_size_name)
     temp = _per_chain(temperature, n, position.device, "temperature")
     return check_batch(position, name), eps, temp
 

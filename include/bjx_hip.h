@@ -520,7 +520,7 @@ int bjx_mgrad_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_o
                      float* logp_out, float* g_out, float* u_x_out, float* u_grad_x_out, float* acceptance_rate_out,
                      uint8_t* is_accepted_out);
 
-/* ---- SGMCMC (blackjax.sgld / sghmc / sgnht; blackjax/sgmcmc/) ---------------------------------
+/* ---- SGMCMC (blackjax.sgld / sghmc / sgnht / csgld; blackjax/sgmcmc/) -------------------------
  * Stochastic-gradient samplers: the gradient estimate `g` comes from the caller (a minibatch gradient), a step is
  * one launch that draws its normals in registers.  `eps` is the step size and `temperature` the temperature, each a
  * scalar or a device (N,) array (`*_per_chain`, which wins when non-null).  Outputs are out of place: no output may
@@ -552,6 +552,26 @@ int bjx_sgnht_step(void* stream, uint32_t key0, uint32_t key1, int64_t chain_off
                    int64_t D, float alpha, float beta, float eps, const float* eps_per_chain, float temperature,
                    const float* temperature_per_chain, const float* q, const float* p, const float* xi,
                    const float* g, float* q_out, float* p_out, float* xi_out);
+/* Contour SGLD, the position half.  energy_pdf is the (N, M) per-chain energy histogram and energy_idx the (N,)
+ * int32 index of each chain's current energy bin, clamped into [1, M - 1] on read.  Per chain, in fp32 in this order
+ * (each log in fp64 rounded once):
+ *   m = 1 + (((zeta T) (log pdf[i] - log pdf[i - 1])) / energy_gap)
+ *   q1 = q + eps (m g) + sqrtf((2 T) eps) normal(k_i, (D,)),  m g one rounding, then one fma per term
+ * A non-positive histogram entry gives a NaN row.  "bad sizes" also covers M < 2.
+ * Replaces: the multiplier of sgmcmc/csgld.py (kernel) and its call of sgmcmc/diffusions.py::overdamped_langevin. */
+int bjx_csgld_step(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int64_t N,
+                   int64_t D, int64_t M, float zeta, float energy_gap, float eps, const float* eps_per_chain,
+                   float temperature, const float* temperature_per_chain, const float* q, const float* g,
+                   const float* energy_pdf, const int32_t* energy_idx, float* q_out);
+/* Contour SGLD, the histogram half, from logdensity (N,), the log-density estimate at the new position:
+ *   x = floorf(((-logdensity - min_energy) / energy_gap) + 1) ; i = !(x >= 1) ? 1 : (x >= M - 1 ? M - 1 : (int)x)
+ *   w = eps_sa * pdf_in[i]^zeta   (pow in fp64 rounded once; zeta == 1: pdf_in[i] itself)
+ *   pdf_out[j] = fma(w, (j == i ? 1 - pdf_in[j] : -pdf_in[j]), pdf_in[j]) ; idx_out = i
+ * NaN and -inf energies give i = 1, +inf gives M - 1.  eps_sa is a scalar or (N,) as eps above.
+ * Replaces: the index and stochastic-approximation update of sgmcmc/csgld.py (kernel). */
+int bjx_csgld_update(void* stream, int64_t N, int64_t M, float zeta, float energy_gap, float min_energy, float eps_sa,
+                     const float* eps_sa_per_chain, const float* logdensity, const float* pdf_in, float* pdf_out,
+                     int32_t* idx_out);
 
 /* ---- Barker (blackjax.barker_proposal; blackjax/mcmc/barker.py) ------------------------------
  * One transition = bjx_barker_propose -> user callable at q1 -> bjx_barker_finish.  `tau` as for MALA.  `imm` is a

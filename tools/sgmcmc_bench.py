@@ -9,11 +9,15 @@ Algorithmic bytes per (chain, dim) element:
   bjx_sghmc_step   r q, p, g    w q, p   20 B  (first step of a transition, momentum drawn: 16; last, position only: 12)
   bjx_sgnht_step   r q, p, g    w q, p   20 B
   bjx_mala_propose r q, g       w q      12 B
+  bjx_csgld_step   r q, g       w q      12 B  (+ 12 B per chain: the index and two histogram entries)
+  bjx_csgld_update r pdf        w pdf     8 B  per (chain, bin) entry of the (N, M) energy histogram, M = 512
 
 After a warm-up every launch of the timed steps is bracketed by HIP events; the figure per entry point is the median.
 bjx_sghmc_step is timed with L = 3: the first / middle / last launch of a transition are told apart by their position in
 it.  At the end bjx_sgld_step and bjx_mala_propose alternate on the same three buffers, which takes the neighbouring
-launches and the operands' history out of the comparison.
+launches and the operands' history out of the comparison.  bjx_csgld_step (contour SGLD's position update: sgld's with a
+per-chain multiplier on the gradient) then alternates with bjx_sgld_step in the same way, and bjx_csgld_update (its
+histogram update) is timed beside a plain PyTorch composition of the same update, bracketed by events as a whole.
 """
 import argparse
 import json
@@ -31,6 +35,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--chains", type=int, default=65536)
 ap.add_argument("--dim", type=int, default=1024)
 ap.add_argument("--step-size", type=float, default=0.01)
+ap.add_argument("--partitions", type=int, default=512, help="bins of csgld's per-chain energy histogram")
 ap.add_argument("--steps", type=int, default=60, help="timed steps per sampler (at least 20: the figure is a median)")
 ap.add_argument("--warmup", type=int, default=20, help="untimed steps per sampler (code objects, the caching allocator)")
 args = ap.parse_args()
@@ -116,12 +121,79 @@ _lib.set_timer(None)
 per_launch["bjx_sgld_step[same buffers]"] = summary(timer.durations_ms("bjx_sgld_step"), 12)
 per_launch["bjx_mala_propose[same buffers]"] = summary(timer.durations_ms("bjx_mala_propose"), 12)
 
+# contour SGLD.  bjx_csgld_step against bjx_sgld_step on the same three buffers; the histogram is csgld.init's and the
+# indices are spread over [1, M - 1], so that the two histogram entries a chain reads differ from chain to chain
+M = args.partitions
+cs = bjx.sgmcmc.csgld
+pdf0 = cs.init(q0, M).energy_pdf
+idx0 = (1 + torch.arange(N, device=dev) % (M - 1)).to(torch.int32)
+timer = _lib.LaunchTimer(("bjx_csgld_step", "bjx_sgld_step"), capacity=2 * args.steps)
+for i in range(args.warmup + args.steps):
+    if i == args.warmup:
+        torch.cuda.synchronize()
+        _lib.set_timer(timer)
+    _lib.call("bjx_csgld_step", _lib.current_stream(), k0, k1, 0, i, N, D, M, 1.0, 10.0, eps, None, 1.0, None,
+              q0.data_ptr(), g0.data_ptr(), pdf0.data_ptr(), idx0.data_ptr(), out.data_ptr())
+    _lib.call("bjx_sgld_step", _lib.current_stream(), k0, k1, 0, i, N, D, eps, None, 1.0, None, q0.data_ptr(),
+              g0.data_ptr(), out.data_ptr())
+torch.cuda.synchronize()
+_lib.set_timer(None)
+per_launch["bjx_csgld_step[same buffers]"] = summary(timer.durations_ms("bjx_csgld_step"), 12)
+per_launch["bjx_sgld_step[same buffers, beside csgld]"] = summary(timer.durations_ms("bjx_sgld_step"), 12)
+
+# bjx_csgld_update against the same update composed of PyTorch operations (zeta = 0.75, so that both take a power), on
+# the same histogram and the same log-densities; energies spread over all bins
+# a power-of-two gap: the bin of an energy does not hang on how a division rounds
+GAP, MIN_E, ZETA, EPS_SA = 8.0, 0.0, 0.75, 0.05
+ld0 = -(GAP * M) * torch.rand(N, device=dev, generator=gen)
+
+
+def torch_update(ld, pdf):
+    idx = torch.floor((-ld - MIN_E) / GAP + 1.0).clamp(1, M - 1).long()[:, None]
+    w = EPS_SA * pdf.gather(1, idx) ** ZETA
+    update = (-pdf).scatter_add_(1, idx, torch.ones_like(w))
+    return pdf + w * update, idx[:, 0].int()
+
+
+def summary_rows(ms):
+    out_ = summary(ms, 8)
+    out_["achieved_TBps"] = 8 * N * M / (out_["median_us"] * 1e-6) / 1e12
+    return out_
+
+
+for _ in range(args.warmup):
+    torch_update(ld0, pdf0)
+    cs.update_energy_histogram(ld0, pdf0, EPS_SA, zeta=ZETA, energy_gap=GAP, min_energy=MIN_E)
+torch.cuda.synchronize()
+timer = _lib.LaunchTimer(("bjx_csgld_update",), capacity=args.steps)
+_lib.set_timer(timer)
+events = []
+for _ in range(args.steps):
+    cs.update_energy_histogram(ld0, pdf0, EPS_SA, zeta=ZETA, energy_gap=GAP, min_energy=MIN_E)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    torch_update(ld0, pdf0)
+    e1.record()
+    events.append((e0, e1))
+torch.cuda.synchronize()
+_lib.set_timer(None)
+per_launch["bjx_csgld_update"] = summary_rows(timer.durations_ms("bjx_csgld_update"))
+per_launch["torch composition of csgld_update"] = summary_rows(np.array([a.elapsed_time(b) for a, b in events]))
+new_pdf, new_idx = cs.update_energy_histogram(ld0, pdf0, EPS_SA, zeta=ZETA, energy_gap=GAP, min_energy=MIN_E)
+t_pdf, t_idx = torch_update(ld0, pdf0)
+assert torch.equal(new_idx, t_idx) and torch.allclose(new_pdf, t_pdf, rtol=1e-5, atol=1e-9)
+
 print(json.dumps({
     "metric": "per-launch time of the SGMCMC step kernels (HIP events, median)",
     "config": {"workload": f"blackjax_amd.sgld / sghmc (L = 3) / sgnht, {N} chains x {D} dims, scalar step size {eps}, "
-                           f"{args.steps} steps after {args.warmup}; bjx_mala_propose in the same process"},
+                           f"{args.steps} steps after {args.warmup}; bjx_mala_propose in the same process; csgld with "
+                           f"{args.partitions} partitions"},
     "sgld_over_mala_propose": per_launch["bjx_sgld_step"]["median_us"] / per_launch["bjx_mala_propose"]["median_us"],
     "sgld_over_mala_propose_same_buffers": (per_launch["bjx_sgld_step[same buffers]"]["median_us"]
                                             / per_launch["bjx_mala_propose[same buffers]"]["median_us"]),
+    "csgld_step_over_sgld_step_same_buffers": (per_launch["bjx_csgld_step[same buffers]"]["median_us"]
+                                               / per_launch["bjx_sgld_step[same buffers, beside csgld]"]["median_us"]),
+    "csgld_update_over_torch_composition": (per_launch["bjx_csgld_update"]["median_us"]
+                                            / per_launch["torch composition of csgld_update"]["median_us"]),
     "per_launch": per_launch,
 }))
