@@ -18,6 +18,7 @@ from . import irmh as _irmh
 from . import mala as _mala
 from . import marginal_latent_gaussian
 from . import nuts as _nuts
+from . import periodic_orbital
 from . import adaptation, chees, diagnostics, distributed, integrators, meads, metrics, optim, random, random_walk, rtc, sgmcmc, smc, targets, util
 from .adaptation import staged_adaptation, window_adaptation
 from .chees import chees_adaptation
@@ -69,6 +70,10 @@ hmc_family = [hmc, nuts, mhmc]  # blackjax/__init__.py:188
 ghmc = GenerateSamplingAPI(_ghmc.as_top_level_api, _ghmc.init, _ghmc.build_kernel)
 # Metropolis-adjusted Langevin (blackjax/mcmc/mala.py): one gradient per transition
 mala = GenerateSamplingAPI(_mala.as_top_level_api, _mala.init, _mala.build_kernel)
+# Periodic orbital MCMC (blackjax/mcmc/periodic_orbital.py, exported by the reference as orbital_hmc): the state is a
+# weighted orbit of `period` samples, rebuilt from one momentum draw by one log-density call on N * period rows
+orbital_hmc = GenerateSamplingAPI(periodic_orbital.as_top_level_api, periodic_orbital.init,
+                                  periodic_orbital.build_kernel)
 # Barker proposal (blackjax/mcmc/barker.py, exported by the reference as barker_proposal): one gradient per
 # transition, step size and diagonal metric tuned by window_adaptation
 barker = GenerateSamplingAPI(_barker.as_top_level_api, _barker.init, _barker.build_kernel)
@@ -102,4 +107,4 @@ sghmc = GenerateSamplingAPI(sgmcmc.sghmc.as_top_level_api, sgmcmc.sghmc.init, sg
 sgnht = GenerateSamplingAPI(sgmcmc.sgnht.as_top_level_api, sgmcmc.sgnht.init, sgmcmc.sgnht.build_kernel)
 csgld = GenerateSamplingAPI(sgmcmc.csgld.as_top_level_api, sgmcmc.csgld.init, sgmcmc.csgld.build_kernel)
 
-__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "barker", "barker_proposal", "elliptical_slice", "mgrad_gaussian", "marginal_latent_gaussian", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "smc", "sgld", "sghmc", "sgnht", "csgld", "sgmcmc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]
+__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "orbital_hmc", "periodic_orbital", "barker", "barker_proposal", "elliptical_slice", "mgrad_gaussian", "marginal_latent_gaussian", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "smc", "sgld", "sghmc", "sgnht", "csgld", "sgmcmc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]

@@ -340,6 +340,14 @@ SIGNATURES.update({
     "bjx_mgrad_finish": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_float, _f32p]
                         + [_f32p] * 17 + [_u8p],
 })
+# include/bjx_hip.h "Periodic orbital" (orbital_hmc: slot choice + momentum draw + the orbit's opening half, closing
+# half kick + weights)
+SIGNATURES.update({
+    "bjx_orbital_open": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_float,
+                         _f32p, _f32p, c_int64, _f32p, c_void_p] + [_f32p] * 6 + [c_void_p, _f32p, _f32p],
+    "bjx_orbital_finish": [c_void_p, c_int64, c_int64, c_int64, c_int, _f32p, c_int64] + [_f32p] * 6
+                          + [c_void_p, _f32p, _f32p],
+})
 INT64_FUNCTIONS = {"bjx_pool_workspace_bytes": [c_int64, c_int64],
                    "bjx_meads_workspace_bytes": [c_int64, c_int64],
                    "bjx_smc_resample_workspace_bytes": [c_int64]}

@@ -481,6 +481,45 @@ int bjx_mala_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_of
                     float* q_out, float* logp_out, float* g_out, float* acceptance_rate_out,
                     uint8_t* is_accepted_out);
 
+/* ---- Periodic orbital (blackjax.orbital_hmc; blackjax/mcmc/periodic_orbital.py) -------------
+ * The state of a chain is a weighted orbit of P slots: positions / grads (N, P, D) = (N * P, D) rows, weights /
+ * logdensities (N, P), directions (N, P) int32.  One transition = bjx_orbital_open -> user callable on the (N * P, D)
+ * rows of q_out -> bjx_orbital_finish.  `eps` is the step size (scalar, or a device (N,) array `eps_per_chain`), `imm`
+ * the diagonal inverse mass matrix ((D,) with imm_stride 0, or (N, D) with imm_stride D), as in bjx_leapfrog_diag.  Keys:
+ *   k_i = split(key, .)[chain_offset+i] (or its step_fold child) ; key_momentum, key_select = split(k_i, 2)
+ * Outputs are out of place: no output may alias an input.  N == 0 is a no-op.
+ *
+ * Opening, per chain:
+ *   cum_j = cumsum(weights)_j (each prefix in fp64, rounded once) ; r = cum_{P-1} * (1 - uniform(key_select)) in fp32
+ *   i = #{j : cum_j < r}, at most P - 1 ; choice_out = i ; (q, logp, g) = slot i ; d = directions[i]
+ *   p = (1 / sqrt(imm)) * normal(key_momentum, (D,))                          (drawn once, as bjx_hmc_momentum_diag)
+ * and for every slot j = 0 .. P-1:  step_out[j] = s_j = float(j - d) * eps  (an fp32 product) and
+ *   drift = 1:  p_out[j] = p_half = fma(s_j / 2, g, p) ;  q_out[j] = fma(s_j, imm * p_half, q)
+ *   drift = 0:  p_out[j] = p ;  q_out[j] = q                     (the selected state repeated: a user bijection's input)
+ * logp_rep_out (N * P,) / g_rep_out (N * P, D), where not NULL, receive the selected logp / g repeated.
+ * q_out, p_out: (N * P, D); step_out: (N * P,); choice_out: (N,) int32.
+ * Replaces: jax/_src/random.py::choice ; mcmc/metrics.py::gaussian_euclidean (sample_momentum) ;
+ * mcmc/periodic_orbital.py::periodic_orbital_proposal (generate) with mcmc/integrators.py::velocity_verlet up to its
+ * log-density evaluation. */
+int bjx_orbital_open(void* stream, uint32_t key0, uint32_t key1, int64_t chain_offset, int64_t step_fold, int64_t N,
+                     int64_t P, int64_t D, int drift, float eps, const float* eps_per_chain, const float* imm,
+                     int64_t imm_stride, const float* weights, const int32_t* directions, const float* positions,
+                     const float* logdensities, const float* grads, float* q_out, float* p_out, float* step_out,
+                     int32_t* choice_out, float* logp_rep_out, float* g_rep_out);
+/* Closing, per chain and slot j, with (logp_j, g_j) the callable's outputs at q_out[j] and s_j = step[j]:
+ *   kick = 1:  momentums_out[j] = p_j = fma(s_j / 2, g_j, p_in[j])   (the closing half kick of velocity_verlet)
+ *   kick = 0:  momentums_out[j] = p_j = p_in[j]                      (a user bijection's momentum; g may be NULL)
+ *   logw_j = logp_j - 0.5 * dot(imm * p_j, p_j)   (fp64 dot rounded once, fp32 subtraction; NaN or +inf -> -inf)
+ * then over the P slots:  m = max logw ; e_j = exp(logw_j - m) (fp64, rounded once) ; S = sum e (fp64, rounded once)
+ *   weights_out[j] = e_j / S ; weights_mean_out = mean(w) ; weights_variance_out = mean((w - mean(w))^2), both fp64
+ *   sums rounded once ; directions_out[j] = j
+ * Replaces: mcmc/periodic_orbital.py::periodic_orbital_proposal (generate: the weights) and kernel (the info), with
+ * mcmc/metrics.py::gaussian_euclidean (kinetic_energy) and jax.nn.softmax. */
+int bjx_orbital_finish(void* stream, int64_t N, int64_t P, int64_t D, int kick, const float* imm,
+                       int64_t imm_stride, const float* step, const float* p_in, const float* logp, const float* g,
+                       float* momentums_out, float* weights_out, int32_t* directions_out, float* weights_mean_out,
+                       float* weights_variance_out);
+
 /* ---- marginal latent Gaussian (blackjax.mgrad_gaussian; blackjax/mcmc/marginal_latent_gaussian.py) ----
  * Gaussian prior N(0, C), C = U diag(Gamma) U^T shared by all chains, arbitrary log-LIKELIHOOD with a gradient (a
  * prior mean is folded into the likelihood: bjx_mgrad_shift).  The kernels work on rows in the prior's eigenbasis,
