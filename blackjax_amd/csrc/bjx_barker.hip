@@ -5,11 +5,13 @@
 // safe_energy_diff.  Livingstone & Zanella 2022.
 //
 // Layout and mapping: bjx_rows.h.  A transition is propose -> user callable -> finish:
-// 12 (16 with a per-chain metric) + 8 + 24 bytes per element.
+// 12 (16 with a per-chain metric) + 8 + 24 bytes per element.  The finish kernels are bjx_finish.h's, with the policy
+// BarkerFinish below.
 #include <math.h>
 
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
+#include "bjx_finish.h"
 #include "bjx_host.h"
 #include "bjx_rows.h"
 
@@ -77,109 +79,23 @@ __device__ __forceinline__ double barker_term(float a0, float a1, float b0, floa
   return softplus64(a) - softplus64(e);
 }
 
-// The per-chain scalar tail (every lane computes it; lane 0 writes): metropolis_accept on safe_energy_diff of the
-// log ratio, key_rmh = split(chain key, 2)[1].
-__device__ __forceinline__ bool barker_accept(Key key, int64_t gidx, int64_t fold, double sum, float lp0,
-                                              float lp1, float* p_acc_out) {
-  const float log_ratio = (lp1 - lp0) + (float)sum;
-  return metropolis_accept(key, gidx, fold, safe_energy_diff(log_ratio), p_acc_out);
-}
-
-// General two-pass finish.  Pass 1 sweeps q0, q1, g0, g1 once and accumulates the fp64 sum; pass 2 copies the
-// accepted or the kept state (wave-uniform source rows) out of place.
-template <int VEC>
-__global__ void __launch_bounds__(kBlock)
-k_barker_finish(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, const float* __restrict__ q0,
-                const float* __restrict__ logp0, const float* __restrict__ g0, const float* __restrict__ q1,
-                const float* __restrict__ logp1, const float* __restrict__ g1, float* __restrict__ q_out,
-                float* __restrict__ logp_out, float* __restrict__ g_out, float* __restrict__ acc_rate_out,
-                uint8_t* __restrict__ is_acc_out) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t r = wave_row0(); r < N; r += wave_row_stride()) {
-    const int64_t base = r * D;
-    double acc = 0.0;
-    for (int64_t j = (int64_t)lane * VEC; j < D; j += 64 * VEC) {
-      float a0[VEC], a1[VEC], b0[VEC], b1[VEC];
-      ldv<VEC>(q0 + base + j, a0);
-      ldv<VEC>(q1 + base + j, a1);
-      ldv<VEC>(g0 + base + j, b0);
-      ldv<VEC>(g1 + base + j, b1);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) acc += barker_term(a0[e], a1[e], b0[e], b1[e]);
-    }
-    acc = wave_sum(acc);
-    const float lp0 = logp0[r], lp1 = logp1[r];
-    float p_acc;
-    const bool accept = barker_accept(key, r + off, fold, acc, lp0, lp1, &p_acc);
-    if (lane == 0) {
-      acc_rate_out[r] = p_acc;
-      is_acc_out[r] = accept ? 1 : 0;
-      logp_out[r] = accept ? lp1 : lp0;
-    }
-    const float* qs = accept ? q1 : q0;
-    const float* gs = accept ? g1 : g0;
-    for (int64_t j = (int64_t)lane * VEC; j < D; j += 64 * VEC) {
-      float a[VEC], b[VEC];
-      ldv<VEC>(qs + base + j, a);
-      ldv<VEC>(gs + base + j, b);
-      stv<VEC>(q_out + base + j, a);
-      stv<VEC>(g_out + base + j, b);
-    }
+// The finish policy (bjx_finish.h): no per-row scalar, one sum, the accept on safe_energy_diff of the log ratio.
+struct BarkerFinish {
+  struct Row {};
+  static constexpr int kSums = 1;
+  static constexpr bool kAux = false;
+  __device__ __forceinline__ Row row(int64_t) const { return {}; }
+  static __device__ __forceinline__ void term(Row, float, float a0, float a1, float b0, float b1, double& sum,
+                                              double&) {
+    sum += barker_term(a0, a1, b0, b1);
   }
-}
-
-// The same for 16-byte rows of at most 256 * NI floats: all four operands stay in registers between the
-// reduction and the select, so the launch moves 16 B read + 8 B written per element and re-reads nothing.
-template <int NI>
-__global__ void __launch_bounds__(kBlock)
-k_barker_finish_res(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, const float* __restrict__ q0,
-                    const float* __restrict__ logp0, const float* __restrict__ g0, const float* __restrict__ q1,
-                    const float* __restrict__ logp1, const float* __restrict__ g1, float* __restrict__ q_out,
-                    float* __restrict__ logp_out, float* __restrict__ g_out, float* __restrict__ acc_rate_out,
-                    uint8_t* __restrict__ is_acc_out) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t r = wave_row0(); r < N; r += wave_row_stride()) {
-    const int64_t base = r * D;
-    F4 Q0[NI], Q1[NI], G0[NI], G1[NI];
-    bool ok[NI];
-#pragma unroll
-    for (int k = 0; k < NI; ++k) {
-      const int64_t j = ((int64_t)lane + 64 * k) * 4;
-      ok[k] = j < D;
-      if (ok[k]) {
-        Q0[k] = ld4(q0 + base + j);
-        Q1[k] = ld4(q1 + base + j);
-        G0[k] = ld4(g0 + base + j);
-        G1[k] = ld4(g1 + base + j);
-      }
-    }
-    double acc = 0.0;
-#pragma unroll
-    for (int k = 0; k < NI; ++k)
-      if (ok[k]) {
-        const float a0[4] = {Q0[k].x, Q0[k].y, Q0[k].z, Q0[k].w}, a1[4] = {Q1[k].x, Q1[k].y, Q1[k].z, Q1[k].w};
-        const float b0[4] = {G0[k].x, G0[k].y, G0[k].z, G0[k].w}, b1[4] = {G1[k].x, G1[k].y, G1[k].z, G1[k].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc += barker_term(a0[e], a1[e], b0[e], b1[e]);
-      }
-    acc = wave_sum(acc);
-    const float lp0 = logp0[r], lp1 = logp1[r];
-    float p_acc;
-    const bool accept = barker_accept(key, r + off, fold, acc, lp0, lp1, &p_acc);
-    if (lane == 0) {
-      acc_rate_out[r] = p_acc;
-      is_acc_out[r] = accept ? 1 : 0;
-      logp_out[r] = accept ? lp1 : lp0;
-    }
-#pragma unroll
-    for (int k = 0; k < NI; ++k)
-      if (ok[k]) {
-        const int64_t j = ((int64_t)lane + 64 * k) * 4;
-        st4(q_out + base + j, accept ? Q1[k] : Q0[k]);
-        st4(g_out + base + j, accept ? G1[k] : G0[k]);
-      }
+  static __device__ __forceinline__ float delta(Row, double sum, double, float lp0, float lp1) {
+    const float log_ratio = (lp1 - lp0) + (float)sum;
+    return safe_energy_diff(log_ratio);
   }
-}
+};
+template <int VEC> constexpr auto k_barker_finish = k_finish<VEC, BarkerFinish>;
+template <int NI> constexpr auto k_barker_finish_res = k_finish_res<NI, BarkerFinish>;
 
 }  // namespace
 
@@ -206,18 +122,11 @@ int bjx_barker_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_
   BJX_CHECK_ARG(q0 && logp0 && g0 && q1 && logp1 && g1 && q_out && logp_out && g_out && acceptance_rate_out &&
                     is_accepted_out,
                 "bjx_barker_finish: null pointer");
-#define BJX_BARKER_FINISH(KERNEL)                                                                          \
-  BJX_LAUNCH_ROWS(KERNEL, N, stream, Key{key0, key1}, chain_offset, step_fold, N, D, q0, logp0, g0, q1, logp1, \
-                  g1, q_out, logp_out, g_out, acceptance_rate_out, is_accepted_out)
-  if (bjx_vec4_ok(D, q0, g0, q1, g1, q_out, g_out)) {
-    if (D <= 256) BJX_BARKER_FINISH(k_barker_finish_res<1>);
-    else if (D <= 512) BJX_BARKER_FINISH(k_barker_finish_res<2>);
-    else if (D <= 1024) BJX_BARKER_FINISH(k_barker_finish_res<4>);
-    else BJX_BARKER_FINISH(k_barker_finish<4>);
-  } else {
-    BJX_BARKER_FINISH(k_barker_finish<1>);
-  }
-#undef BJX_BARKER_FINISH
+  // no shared operand and no carried pair: the seven nullptr
+  BJX_LAUNCH_ROWS_RES(bjx_vec4_ok(D, q0, g0, q1, g1, q_out, g_out), D, k_barker_finish_res, k_barker_finish, N, stream,
+                      Key{key0, key1}, chain_offset, step_fold, N, D, BarkerFinish{}, q0, logp0, g0, q1, logp1, g1, q_out,
+                      logp_out, g_out, acceptance_rate_out, is_accepted_out, nullptr, nullptr, nullptr, nullptr, nullptr,
+                      nullptr, nullptr);
   return bjx_check_launch("bjx_barker_finish");
 }
 

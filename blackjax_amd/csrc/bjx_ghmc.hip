@@ -373,20 +373,11 @@ int bjx_ghmc_finish(void* stream, int64_t N, int64_t D, float eps, const float* 
                 "bjx_ghmc_finish: null pointer");
   BJX_CHECK_ARG(imm_stride == 0 || imm_stride == D, "bjx_ghmc_finish: imm_stride must be 0 or D");
   BJX_CHECK_ARG(skip_begin <= skip_end, "bjx_ghmc_finish: skip_begin must not exceed skip_end");
-#define BJX_FINISH(KERNEL)                                                                                      \
-  BJX_LAUNCH_ROWS(KERNEL, N, stream, N, D, eps, eps_per_chain, imm, imm_stride, divergence_threshold, q0, logp0, g0, \
-                  ke0, p, slice, p_prev, slice_prev, q1, p_half, logp1, g1, skip_begin, skip_end, q_out, p_out,      \
-                  logp_out, g_out, slice_out, acceptance_rate_out, is_accepted_out, is_divergent_out, energy_out,    \
-                  p_end_out)
-  if (bjx_vec4_ok(D, imm, q0, g0, p, p_prev, q1, p_half, g1, q_out, p_out, g_out, p_end_out)) {
-    if (D <= 256) BJX_FINISH(k_ghmc_finish_res<1>);
-    else if (D <= 512) BJX_FINISH(k_ghmc_finish_res<2>);
-    else if (D <= 1024) BJX_FINISH(k_ghmc_finish_res<4>);
-    else BJX_FINISH(k_ghmc_finish<4>);
-  } else {
-    BJX_FINISH(k_ghmc_finish<1>);
-  }
-#undef BJX_FINISH
+  BJX_LAUNCH_ROWS_RES(bjx_vec4_ok(D, imm, q0, g0, p, p_prev, q1, p_half, g1, q_out, p_out, g_out, p_end_out), D,
+                      k_ghmc_finish_res, k_ghmc_finish, N, stream, N, D, eps, eps_per_chain, imm, imm_stride,
+                      divergence_threshold, q0, logp0, g0, ke0, p, slice, p_prev, slice_prev, q1, p_half, logp1, g1,
+                      skip_begin, skip_end, q_out, p_out, logp_out, g_out, slice_out, acceptance_rate_out,
+                      is_accepted_out, is_divergent_out, energy_out, p_end_out);
   return bjx_check_launch("bjx_ghmc_finish");
 }
 

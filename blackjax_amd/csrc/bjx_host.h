@@ -47,6 +47,16 @@ static inline bool bjx_vec4_ok(int64_t D, P... ptrs) {
     if (VEC4_OK) BJX_LAUNCH_ROWS(KERNEL<4>, ROWS, STREAM, __VA_ARGS__);  \
     else BJX_LAUNCH_ROWS(KERNEL<1>, ROWS, STREAM, __VA_ARGS__);          \
   } while (0)
+// The same for a finish with a register-resident form.  KERNEL_RES<NI> holds a 16-byte row of at most 256 * NI floats
+// (NI = 1, 2, 4); the two-pass KERNEL<4> takes longer rows and KERNEL<1> those that are not VEC4_OK.
+#define BJX_LAUNCH_ROWS_RES(VEC4_OK, D, KERNEL_RES, KERNEL, ROWS, STREAM, ...)                \
+  do {                                                                                        \
+    if (!(VEC4_OK)) BJX_LAUNCH_ROWS(KERNEL<1>, ROWS, STREAM, __VA_ARGS__);                    \
+    else if ((D) <= 256) BJX_LAUNCH_ROWS(KERNEL_RES<1>, ROWS, STREAM, __VA_ARGS__);           \
+    else if ((D) <= 512) BJX_LAUNCH_ROWS(KERNEL_RES<2>, ROWS, STREAM, __VA_ARGS__);           \
+    else if ((D) <= 1024) BJX_LAUNCH_ROWS(KERNEL_RES<4>, ROWS, STREAM, __VA_ARGS__);          \
+    else BJX_LAUNCH_ROWS(KERNEL<4>, ROWS, STREAM, __VA_ARGS__);                               \
+  } while (0)
 
 // Store policy of the cache-resident HMC loop kernels (flat leapfrog, gradient-only Gaussian callable): p, q and g
 // written through L2 (st4_wt, bjx_device.h).  BJX_LF_POLICY=0 gives plain stores (A/B: tools/README.md); read

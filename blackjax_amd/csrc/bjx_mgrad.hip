@@ -13,11 +13,13 @@
 //                      diagonal prior, two-pass           + the two selected rows again     32
 //                      dense prior, resident              + r position, gradient, w both    40
 //                      dense prior, two-pass                                                48
-// VGPRs (kernel-resource-usage remark of the gfx950 build), no scratch anywhere: see the kernels.
+// The finish kernels are bjx_finish.h's, with the policy MgradFinish below.  VGPRs (kernel-resource-usage remark of
+// the gfx950 build), no scratch anywhere: see the kernels, and bjx_finish.h for the finish.
 #include <math.h>
 
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
+#include "bjx_finish.h"
 #include "bjx_host.h"
 #include "bjx_rows.h"
 
@@ -97,162 +99,41 @@ k_mgrad_shift(int64_t N, int64_t D, const float* __restrict__ shift, const float
   }
 }
 
-// One element's terms of the two dots of the acceptance ratio:
+// The finish policy (bjx_finish.h).  The row pair is the eigenbasis pair (a = U_x / U_y, b = U_grad_x / U_grad_y), aux is
+// Gamma and the sums are the two dots of the acceptance ratio:
 //   t_x = Gamma_1 (U_x / (0.5 delta) + 0.5 U_grad_x), t_y likewise from the proposal
 //   hxy += (U_x - t_y) (Gamma_3 U_grad_y) ; hyx += (U_y - t_x) (Gamma_3 U_grad_x)      (fp32 factors, fp64 products)
-__device__ __forceinline__ void mgrad_terms(float gam, float delta, float hd, float ux, float ugx, float uy, float ugy,
-                                            double* hxy, double* hyx) {
-  float g1, g3;
-  mgrad_coef(gam, delta, &g1, &g3);
-  const float tx = g1 * fmaf(0.5f, ugx, ux / hd);
-  const float ty = g1 * fmaf(0.5f, ugy, uy / hd);
-  *hxy += (double)(ux - ty) * (double)(g3 * ugy);
-  *hyx += (double)(uy - tx) * (double)(g3 * ugx);
-}
-
-// The per-chain scalar tail (every lane computes it; lane 0 writes): log_ratio = ((logp_y - logp_x) + hxy) - hyx,
-// metropolis_accept on safe_energy_diff(log_ratio), u_key = split(chain key, 2)[1].
-__device__ __forceinline__ bool mgrad_accept(Key key, int64_t gidx, int64_t fold, double hxy, double hyx, float lpx,
-                                             float lpy, float* p_acc_out) {
-  const float lr = ((lpy - lpx) + (float)hxy) - (float)hyx;
-  return metropolis_accept(key, gidx, fold, safe_energy_diff(lr), p_acc_out);
-}
-
-// General two-pass finish.  Pass 1 sweeps the four eigenbasis rows once and accumulates both dots; pass 2 copies the
-// accepted or the kept state (wave-uniform source rows) out of place.  With a dense prior (x_out non-null) the state
-// has position and gradient beside their eigenbasis images; with a diagonal prior they are the same arrays and only
-// the eigenbasis pair is written.  VEC = 4 / 1: 88 / 71 VGPRs.
-template <int VEC>
-__global__ void __launch_bounds__(kBlock)
-k_mgrad_finish(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, float delta_s,
-               const float* __restrict__ delta_pc, const float* __restrict__ gamma, const float* __restrict__ x,
-               const float* __restrict__ logpx, const float* __restrict__ gx, const float* __restrict__ ux,
-               const float* __restrict__ ugx, const float* __restrict__ y, const float* __restrict__ logpy,
-               const float* __restrict__ gy, const float* __restrict__ uy, const float* __restrict__ ugy,
-               float* __restrict__ x_out, float* __restrict__ logp_out, float* __restrict__ g_out,
-               float* __restrict__ ux_out, float* __restrict__ ugx_out, float* __restrict__ acc_rate_out,
-               uint8_t* __restrict__ is_acc_out) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t r = wave_row0(); r < N; r += wave_row_stride()) {
+//   log_ratio = ((logp_y - logp_x) + hxy) - hyx
+// With a dense prior (x_out non-null) the state has position and gradient beside their eigenbasis images, the carried
+// pair; with a diagonal prior they are the same arrays and only the eigenbasis pair is written.
+struct MgradFinish {
+  float delta_s;
+  const float* delta_pc;
+  struct Row {
+    float delta, hd;
+  };
+  static constexpr int kSums = 2;
+  static constexpr bool kAux = true;
+  __device__ __forceinline__ Row row(int64_t r) const {
     const float delta = delta_pc ? delta_pc[r] : delta_s;
-    const float hd = 0.5f * delta;
-    const int64_t base = r * D;
-    double hxy = 0.0, hyx = 0.0;
-    for (int64_t j = (int64_t)lane * VEC; j < D; j += 64 * VEC) {
-      float a0[VEC], b0[VEC], a1[VEC], b1[VEC], gam[VEC];
-      ldv<VEC>(ux + base + j, a0);
-      ldv<VEC>(ugx + base + j, b0);
-      ldv<VEC>(uy + base + j, a1);
-      ldv<VEC>(ugy + base + j, b1);
-      ldv<VEC>(gamma + j, gam);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) mgrad_terms(gam[e], delta, hd, a0[e], b0[e], a1[e], b1[e], &hxy, &hyx);
-    }
-    hxy = wave_sum(hxy);
-    hyx = wave_sum(hyx);
-    const float lp0 = logpx[r], lp1 = logpy[r];
-    float p_acc;
-    const bool accept = mgrad_accept(key, r + off, fold, hxy, hyx, lp0, lp1, &p_acc);
-    if (lane == 0) {
-      acc_rate_out[r] = p_acc;
-      is_acc_out[r] = accept ? 1 : 0;
-      logp_out[r] = accept ? lp1 : lp0;
-    }
-    const float* us = accept ? uy : ux;
-    const float* ugs = accept ? ugy : ugx;
-    for (int64_t j = (int64_t)lane * VEC; j < D; j += 64 * VEC) {
-      float a[VEC], b[VEC];
-      ldv<VEC>(us + base + j, a);
-      ldv<VEC>(ugs + base + j, b);
-      stv<VEC>(ux_out + base + j, a);
-      stv<VEC>(ugx_out + base + j, b);
-    }
-    if (x_out) {
-      const float* qs = accept ? y : x;
-      const float* gs = accept ? gy : gx;
-      for (int64_t j = (int64_t)lane * VEC; j < D; j += 64 * VEC) {
-        float a[VEC], b[VEC];
-        ldv<VEC>(qs + base + j, a);
-        ldv<VEC>(gs + base + j, b);
-        stv<VEC>(x_out + base + j, a);
-        stv<VEC>(g_out + base + j, b);
-      }
-    }
+    return {delta, 0.5f * delta};
   }
-}
-
-// The same for 16-byte rows of at most 256 * NI floats: the four eigenbasis rows stay in registers between the
-// reduction and the select and are not read again; the position and gradient of a dense prior are read once, from
-// the selected rows.  NI = 1 / 2 / 4: 75 / 78 / 110 VGPRs.
-template <int NI>
-__global__ void __launch_bounds__(kBlock)
-k_mgrad_finish_res(Key key, int64_t off, int64_t fold, int64_t N, int64_t D, float delta_s,
-                   const float* __restrict__ delta_pc, const float* __restrict__ gamma,
-                   const float* __restrict__ x, const float* __restrict__ logpx, const float* __restrict__ gx,
-                   const float* __restrict__ ux, const float* __restrict__ ugx, const float* __restrict__ y,
-                   const float* __restrict__ logpy, const float* __restrict__ gy, const float* __restrict__ uy,
-                   const float* __restrict__ ugy, float* __restrict__ x_out, float* __restrict__ logp_out,
-                   float* __restrict__ g_out, float* __restrict__ ux_out, float* __restrict__ ugx_out,
-                   float* __restrict__ acc_rate_out, uint8_t* __restrict__ is_acc_out) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t r = wave_row0(); r < N; r += wave_row_stride()) {
-    const float delta = delta_pc ? delta_pc[r] : delta_s;
-    const float hd = 0.5f * delta;
-    const int64_t base = r * D;
-    F4 A0[NI], B0[NI], A1[NI], B1[NI];
-    bool ok[NI];
-#pragma unroll
-    for (int k = 0; k < NI; ++k) {
-      const int64_t j = ((int64_t)lane + 64 * k) * 4;
-      ok[k] = j < D;
-      if (ok[k]) {
-        A0[k] = ld4(ux + base + j);
-        B0[k] = ld4(ugx + base + j);
-        A1[k] = ld4(uy + base + j);
-        B1[k] = ld4(ugy + base + j);
-      }
-    }
-    double hxy = 0.0, hyx = 0.0;
-#pragma unroll
-    for (int k = 0; k < NI; ++k)
-      if (ok[k]) {
-        const F4 GM = ld4(gamma + ((int64_t)lane + 64 * k) * 4);
-        const float gam[4] = {GM.x, GM.y, GM.z, GM.w};
-        const float a0[4] = {A0[k].x, A0[k].y, A0[k].z, A0[k].w}, b0[4] = {B0[k].x, B0[k].y, B0[k].z, B0[k].w};
-        const float a1[4] = {A1[k].x, A1[k].y, A1[k].z, A1[k].w}, b1[4] = {B1[k].x, B1[k].y, B1[k].z, B1[k].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) mgrad_terms(gam[e], delta, hd, a0[e], b0[e], a1[e], b1[e], &hxy, &hyx);
-      }
-    hxy = wave_sum(hxy);
-    hyx = wave_sum(hyx);
-    const float lp0 = logpx[r], lp1 = logpy[r];
-    float p_acc;
-    const bool accept = mgrad_accept(key, r + off, fold, hxy, hyx, lp0, lp1, &p_acc);
-    if (lane == 0) {
-      acc_rate_out[r] = p_acc;
-      is_acc_out[r] = accept ? 1 : 0;
-      logp_out[r] = accept ? lp1 : lp0;
-    }
-#pragma unroll
-    for (int k = 0; k < NI; ++k)
-      if (ok[k]) {
-        const int64_t j = ((int64_t)lane + 64 * k) * 4;
-        st4(ux_out + base + j, accept ? A1[k] : A0[k]);
-        st4(ugx_out + base + j, accept ? B1[k] : B0[k]);
-      }
-    if (x_out) {
-      const float* qs = accept ? y : x;
-      const float* gs = accept ? gy : gx;
-#pragma unroll
-      for (int k = 0; k < NI; ++k)
-        if (ok[k]) {
-          const int64_t j = ((int64_t)lane + 64 * k) * 4;
-          st4(x_out + base + j, ld4(qs + base + j));
-          st4(g_out + base + j, ld4(gs + base + j));
-        }
-    }
+  static __device__ __forceinline__ void term(Row row, float gam, float ux, float uy, float ugx, float ugy, double& hxy,
+                                              double& hyx) {
+    float g1, g3;
+    mgrad_coef(gam, row.delta, &g1, &g3);
+    const float tx = g1 * fmaf(0.5f, ugx, ux / row.hd);
+    const float ty = g1 * fmaf(0.5f, ugy, uy / row.hd);
+    hxy += (double)(ux - ty) * (double)(g3 * ugy);
+    hyx += (double)(uy - tx) * (double)(g3 * ugx);
   }
-}
+  static __device__ __forceinline__ float delta(Row, double hxy, double hyx, float lpx, float lpy) {
+    const float lr = ((lpy - lpx) + (float)hxy) - (float)hyx;
+    return safe_energy_diff(lr);
+  }
+};
+template <int VEC> constexpr auto k_mgrad_finish = k_finish<VEC, MgradFinish>;
+template <int NI> constexpr auto k_mgrad_finish_res = k_finish_res<NI, MgradFinish>;
 
 }  // namespace
 
@@ -294,19 +175,11 @@ int bjx_mgrad_finish(void* stream, uint32_t key0, uint32_t key1, int64_t chain_o
   const bool dense = x_out != nullptr;
   BJX_CHECK_ARG(dense ? (x && g_x && y && g_y && g_out) : (!x && !g_x && !y && !g_y && !g_out),
                 "bjx_mgrad_finish: x, g_x, y, g_y, x_out, g_out are given together (dense prior) or not at all");
-#define BJX_MGRAD_FINISH(KERNEL)                                                                                   \
-  BJX_LAUNCH_ROWS(KERNEL, N, stream, Key{key0, key1}, chain_offset, step_fold, N, D, delta, delta_per_chain, gamma, \
-                  x, logp_x, g_x, u_x, u_grad_x, y, logp_y, g_y, u_y, u_grad_y, x_out, logp_out, g_out, u_x_out,    \
-                  u_grad_x_out, acceptance_rate_out, is_accepted_out)
-  if (bjx_vec4_ok(D, gamma, x, g_x, u_x, u_grad_x, y, g_y, u_y, u_grad_y, x_out, g_out, u_x_out, u_grad_x_out)) {
-    if (D <= 256) BJX_MGRAD_FINISH(k_mgrad_finish_res<1>);
-    else if (D <= 512) BJX_MGRAD_FINISH(k_mgrad_finish_res<2>);
-    else if (D <= 1024) BJX_MGRAD_FINISH(k_mgrad_finish_res<4>);
-    else BJX_MGRAD_FINISH(k_mgrad_finish<4>);
-  } else {
-    BJX_MGRAD_FINISH(k_mgrad_finish<1>);
-  }
-#undef BJX_MGRAD_FINISH
+  BJX_LAUNCH_ROWS_RES(
+      bjx_vec4_ok(D, gamma, x, g_x, u_x, u_grad_x, y, g_y, u_y, u_grad_y, x_out, g_out, u_x_out, u_grad_x_out), D,
+      k_mgrad_finish_res, k_mgrad_finish, N, stream, Key{key0, key1}, chain_offset, step_fold, N, D,
+      MgradFinish{delta, delta_per_chain}, u_x, logp_x, u_grad_x, u_y, logp_y, u_grad_y, u_x_out, logp_out, u_grad_x_out,
+      acceptance_rate_out, is_accepted_out, gamma, x, g_x, y, g_y, x_out, g_out);
   return bjx_check_launch("bjx_mgrad_finish");
 }
 

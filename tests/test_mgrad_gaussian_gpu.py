@@ -99,7 +99,10 @@ def test_mgrad_dense_transitions_match_restatement(dev, N, D, per_chain, delta, 
                 per_chain, n_steps)
 
 
-@pytest.mark.parametrize("N,D,per_chain,delta", [(37, 10, True, 2.0), (24, 64, True, 1.0), (6, 1032, False, 0.25)])
+# 4-byte sweep; resident NI = 1, 2, 4 (the last at its largest row); 16-byte two-pass: every form of the finish
+# without the position / gradient pair of a dense prior
+@pytest.mark.parametrize("N,D,per_chain,delta", [(37, 10, True, 2.0), (24, 64, True, 1.0), (33, 260, True, 0.25),
+                                                 (9, 1024, True, 0.5), (6, 1032, False, 0.25)])
 def test_mgrad_diagonal_prior_matches_restatement(dev, N, D, per_chain, delta):
     """A 1-d covariance: U = I, no GEMM, and no eigenbasis copy -- state.U_x shares storage with state.position."""
     svd, inv_var, x0, delta = _case(N, D, per_chain, delta, diagonal=True)
