@@ -99,6 +99,13 @@ irmh = GenerateSamplingAPI(_irmh.as_top_level_api, _irmh.init, _irmh.build_kerne
 tempered_smc = GenerateSamplingAPI(smc.tempered.as_top_level_api, smc.tempered.init, smc.tempered.build_kernel)
 adaptive_tempered_smc = GenerateSamplingAPI(smc.adaptive_tempered.as_top_level_api, smc.adaptive_tempered.init,
                                             smc.adaptive_tempered.build_kernel)
+# Persistent-sampling SMC (blackjax/smc/persistent_sampling.py, adaptive_persistent_sampling.py): every iteration weighs
+# the particles of all earlier ones; the mixture denominator, the grid-wide log-sum-exp and the ESS solve are HIP kernels
+persistent_sampling_smc = GenerateSamplingAPI(smc.persistent_sampling.as_top_level_api, smc.persistent_sampling.init,
+                                              smc.persistent_sampling.build_kernel)
+adaptive_persistent_sampling_smc = GenerateSamplingAPI(smc.adaptive_persistent_sampling.as_top_level_api,
+                                                       smc.adaptive_persistent_sampling.init,
+                                                       smc.adaptive_persistent_sampling.build_kernel)
 # Stochastic-gradient MCMC (blackjax/sgmcmc/sgld.py, sghmc.py, sgnht.py, csgld.py): the gradient is a minibatch estimate
 # from the user's callable, the noise draw + diffusion update (+ thermostat) is one fused launch per step; csgld adds
 # one launch for its per-chain energy histogram
@@ -107,4 +114,4 @@ sghmc = GenerateSamplingAPI(sgmcmc.sghmc.as_top_level_api, sgmcmc.sghmc.init, sg
 sgnht = GenerateSamplingAPI(sgmcmc.sgnht.as_top_level_api, sgmcmc.sgnht.init, sgmcmc.sgnht.build_kernel)
 csgld = GenerateSamplingAPI(sgmcmc.csgld.as_top_level_api, sgmcmc.csgld.init, sgmcmc.csgld.build_kernel)
 
-__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "orbital_hmc", "periodic_orbital", "barker", "barker_proposal", "elliptical_slice", "mgrad_gaussian", "marginal_latent_gaussian", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "smc", "sgld", "sghmc", "sgnht", "csgld", "sgmcmc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]
+__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "orbital_hmc", "periodic_orbital", "barker", "barker_proposal", "elliptical_slice", "mgrad_gaussian", "marginal_latent_gaussian", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "persistent_sampling_smc", "adaptive_persistent_sampling_smc", "smc", "sgld", "sghmc", "sgnht", "csgld", "sgmcmc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]

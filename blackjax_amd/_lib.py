@@ -310,6 +310,11 @@ SIGNATURES.update({
     "bjx_smc_reweight": [c_void_p, c_int64] + [_f32p] * 6,
     "bjx_smc_log_ess": [c_void_p, c_int64, _f32p, _f32p],
     "bjx_smc_ess_solve": [c_void_p, c_int64, _f32p, c_float, _f32p, _f32p, _f32p, _f32p],
+    # persistent sampling (bjx_smc_persistent_tile returns the reduction's tile size, not a status)
+    "bjx_smc_persistent_tile": [],
+    "bjx_smc_persistent_denominator": [c_void_p, c_int64, c_int64, _f32p, _f32p, _f32p, _f32p],
+    "bjx_smc_persistent_weights": [c_void_p, c_int64, _f32p, _f32p, _f32p, c_void_p, _f32p, _f32p, _f32p],
+    "bjx_smc_persistent_ess_solve": [c_void_p, c_int64, _f32p, _f32p, c_float, _f32p, c_void_p, _f32p, _f32p],
 })
 # include/bjx_hip.h "random walk" (rmh / additive_step_random_walk / irmh: keyed noise, fused propose, accept + select)
 SIGNATURES.update({
@@ -350,7 +355,8 @@ SIGNATURES.update({
 })
 INT64_FUNCTIONS = {"bjx_pool_workspace_bytes": [c_int64, c_int64],
                    "bjx_meads_workspace_bytes": [c_int64, c_int64],
-                   "bjx_smc_resample_workspace_bytes": [c_int64]}
+                   "bjx_smc_resample_workspace_bytes": [c_int64],
+                   "bjx_smc_persistent_workspace_bytes": [c_int64]}
 
 _lib = None
 

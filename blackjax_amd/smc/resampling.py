@@ -2,7 +2,8 @@
 
 Mirrors blackjax/smc/resampling.py ``systematic`` and ``stratified`` (``searchsorted`` of the positions
 ``(i + u_i) / num_samples`` in the cumulative weights, clipped to ``N - 1``).  ``multinomial`` and ``residual`` are
-out of scope.
+out of scope.  ``num_samples`` need not equal ``N``: persistent sampling (``blackjax_amd.smc.persistent_sampling``)
+draws ``N`` ancestors from the ``i * N`` weights of its persistent set.
 
 The cumulative weights are held in 2^-62 fixed point (``bjx_smc_resample``, include/bjx_hip.h "SMC"): integer sums
 do not depend on how the prefix scan is tiled, so the ancestors are reproducible bit for bit

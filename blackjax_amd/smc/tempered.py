@@ -20,8 +20,8 @@ A particle whose log-likelihood is ``-inf`` or NaN gets weight 0.  If EVERY part
 temperature moved) the weights are NaN and the increment is ``-inf``; no host check is made for it.  With
 ``lam_new == lam_old`` the weights are uniform whatever the log-likelihoods are.
 
-Out of scope: ``multinomial`` / ``residual`` resampling, persistent, partial-posteriors, pretuning and waste-free SMC,
-inner-kernel tuning, pytrees of particles, and sharding the particles across GPUs (resampling is global: there is no
+Out of scope: ``multinomial`` / ``residual`` resampling, partial-posteriors, pretuning and waste-free SMC (persistent
+sampling is ``blackjax_amd.smc.persistent_sampling``), inner-kernel tuning, pytrees of particles, and sharding the particles across GPUs (resampling is global: there is no
 ``chain_offset`` here).
 """
 from __future__ import annotations

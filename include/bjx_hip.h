@@ -760,6 +760,37 @@ int bjx_smc_log_ess(void* stream, int64_t N, const float* log_weights, float* lo
 int bjx_smc_ess_solve(void* stream, int64_t N, const float* loglik, float target_ess, const float* max_delta,
                       const float* lam_old, float* delta_out, float* lam_new_out);
 
+/* Persistent sampling (blackjax.persistent_sampling_smc / adaptive_persistent_sampling_smc).  Iteration i weighs
+ * the P = i * N particles of ALL earlier iterations against the mixture of their tempered targets:
+ *   den_j = logsumexp_{s < n_terms}(a_sj - log_Z[s]) - log(n_terms), a_sj = schedule[s] * loglik[j] in fp32 (exactly 0
+ *           when schedule[s] == 0, whatever loglik[j] is); the rest in fp64, the maximum subtracted, rounded once
+ *   lw_j  = (double)(fp32 *lam * loglik[j]) - (double) den_j ; a NaN or -inf lw_j is a particle of weight 0
+ *   lse   = logsumexp_j(lw_j) (fp64) ; *log_Z_out = lse - log P ; weights_out = exp(lw - lse) ;
+ *           log_weights_out = lw - lse (-inf for a particle of weight 0).  No particle of positive weight: both
+ *           arrays NaN, *log_Z_out = -inf.
+ * P reaches 2^24, so the reductions use the whole device: one workgroup per tile of bjx_smc_persistent_tile()
+ * particles writes the tile's (max, S1, S2) in fp64 into the workspace and a later launch of one workgroup adds them
+ * (launch-separated: no workgroup waits on another).  The tiling depends on P alone, so results are reproducible bit
+ * for bit.  workspace: bjx_smc_persistent_workspace_bytes(P) bytes (0 for a P outside [1, 2^24]), 8-byte aligned,
+ * contents scratch.  1 <= n_terms ; any of the three outputs of bjx_smc_persistent_weights may be null, not all.
+ * Replaces: smc/persistent_sampling.py::compute_log_persistent_weights, compute_log_Z, compute_persistent_weights. */
+int bjx_smc_persistent_tile(void);
+int64_t bjx_smc_persistent_workspace_bytes(int64_t P);
+int bjx_smc_persistent_denominator(void* stream, int64_t P, int64_t n_terms, const float* loglik,
+                                   const float* schedule, const float* log_Z, float* den_out);
+int bjx_smc_persistent_weights(void* stream, int64_t P, const float* loglik, const float* den, const float* lam,
+                               void* workspace, float* log_weights_out, float* weights_out, float* log_Z_out);
+/* The next temperature: f(d) = log_ess(lw at lam = *lam_old + d) - log(target), target an ABSOLUTE effective sample
+ * size (the caller's N * target_ess; it may exceed N, never P's bound 2^24), log_ess = 2 log S1 - log S2 in fp64.
+ *   f(1 - *lam_old) >= 0: delta = 1 - *lam_old and *lam_new_out = 1.0f exactly ; else 30 halvings of [0, 1 - *lam_old]
+ *   in fp32, left end moved to mid when f(mid) >= 0, delta = the left end, *lam_new_out = *lam_old + delta.  A target
+ *   no temperature reaches gives delta = 0 and *lam_new_out = *lam_old bit for bit.
+ * 31 evaluations of f, each a tile launch and a one-workgroup launch that moves the bracket kept in the workspace:
+ * 62 launches whatever the data; once the whole interval is taken the remaining ones return at once.
+ * Replaces: smc/adaptive_persistent_sampling.py::calculate_lambda ; smc/ess.py::log_ess ; smc/solver.py::dichotomy. */
+int bjx_smc_persistent_ess_solve(void* stream, int64_t P, const float* loglik, const float* den, float target,
+                                 const float* lam_old, void* workspace, float* delta_out, float* lam_new_out);
+
 /* Built-in synthetic targets (value + gradient in one pass, fp64-accumulated logp) used
  * as the "user callable" by the bench and parity tests.
  *   diag gaussian:  g = -(q*inv_var) ; logp = 0.5 * sum q*g     (tests/fixtures.py:60-78)
