@@ -310,6 +310,13 @@ SIGNATURES.update({
     "bjx_smc_reweight": [c_void_p, c_int64] + [_f32p] * 6,
     "bjx_smc_log_ess": [c_void_p, c_int64, _f32p, _f32p],
     "bjx_smc_ess_solve": [c_void_p, c_int64, _f32p, c_float, _f32p, _f32p, _f32p, _f32p],
+    # multinomial / residual resampling, the waste-free row store, column moments (bjx_smc_moments_tile returns the
+    # moments' row tile, not a status)
+    "bjx_smc_resample_sorted": [c_void_p, c_uint32, c_uint32, ctypes.c_int32, c_int64, c_int64, _f32p, c_void_p,
+                                c_void_p, c_void_p],
+    "bjx_smc_scatter_rows": [c_void_p, c_int64, c_int64, _f32p, c_int64, c_int64, _f32p],
+    "bjx_smc_moments_tile": [],
+    "bjx_smc_particle_moments": [c_void_p, c_int64, c_int64, _f32p, c_void_p, _f32p, _f32p],
     # persistent sampling (bjx_smc_persistent_tile returns the reduction's tile size, not a status)
     "bjx_smc_persistent_tile": [],
     "bjx_smc_persistent_denominator": [c_void_p, c_int64, c_int64, _f32p, _f32p, _f32p, _f32p],
@@ -356,6 +363,8 @@ SIGNATURES.update({
 INT64_FUNCTIONS = {"bjx_pool_workspace_bytes": [c_int64, c_int64],
                    "bjx_meads_workspace_bytes": [c_int64, c_int64],
                    "bjx_smc_resample_workspace_bytes": [c_int64],
+                   "bjx_smc_resample_sorted_workspace_bytes": [c_int64, c_int64],
+                   "bjx_smc_particle_moments_workspace_bytes": [c_int64, c_int64],
                    "bjx_smc_persistent_workspace_bytes": [c_int64]}
 
 _lib = None

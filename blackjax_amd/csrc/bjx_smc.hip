@@ -2,7 +2,9 @@
 //
 // Reference: blackjax/smc/base.py (step), smc/resampling.py (systematic, stratified: _systematic_or_stratified,
 // _sorted_uniforms' callers), smc/ess.py (log_ess, ess_solver), smc/solver.py (dichotomy),
-// smc/tempered.py (build_kernel: log_weights_fn, tempered_logposterior_fn).
+// smc/tempered.py (build_kernel: log_weights_fn, tempered_logposterior_fn); smc/resampling.py (multinomial, residual,
+// _sorted_uniforms), smc/waste_free.py (update_waste_free: the layout of the kept states), smc/tuning/from_particles.py
+// (particles_means, particles_stds).
 //
 // Resampling works on cumulative weights in 2^-62 fixed point: integer addition is associative, so the prefix sum
 // is the same whatever the tiling, and the ancestor search compares integers.  The scan is launch-separated (tile
@@ -321,12 +323,181 @@ k_ess_solve(int64_t N, const float* __restrict__ ll, double log_target, const fl
   }
 }
 
+// ---- multinomial / residual resampling: sorted uniforms from an integer prefix sum of exponentials ----------
+constexpr double kTwo24 = 16777216.0;
+constexpr uint64_t kMask62 = ((uint64_t)1 << 62) - 1;
+
+// resampling.py::_sorted_uniforms, the exponentials: ef_k = (int64) floor((double) e_k * 2^24) with
+// e_k = -log1p(-u_k) correctly rounded to fp32 and u_k = uniform(key, (count,))[k].  e_k < 16, so the sum of
+// 2^24 + 1 of them stays below 2^53.
+__global__ void __launch_bounds__(kBlock) k_exp_fixed(Key key, int64_t count, int64_t* __restrict__ ef) {
+  for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += (int64_t)gridDim.x * kBlock) {
+    const float u = fmaxf(0.0f, unit_float(key_bits32(key, (uint64_t)k)));
+    const float e = bjx_neg_log1p(-u);
+    ef[k] = (int64_t)floor((double)e * kTwo24);
+  }
+}
+
+// pos_i = Z_i / max(Z_M, 1) in fp64 (both conversions exact, the division rounded once): the i-th sorted uniform
+__device__ __forceinline__ double sorted_uniform(const int64_t* __restrict__ z, int64_t M, int64_t i) {
+  const int64_t zm = z[M];
+  return (double)z[i] / (double)(zm > 1 ? zm : 1);
+}
+
+// #{j < N : c_j < t}
+__device__ __forceinline__ int64_t count_below(const int64_t* __restrict__ c, int64_t N, int64_t t) {
+  int64_t lo = 0, hi = N;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (c[mid] < t) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// resampling.py::multinomial: ancestor_i = min(N - 1, #{j : C_j < (int64)(pos_i * 2^62)})
+__global__ void __launch_bounds__(kBlock)
+k_resample_multinomial(int64_t N, int64_t M, const int64_t* __restrict__ cum, const int64_t* __restrict__ z,
+                       int32_t* __restrict__ ancestors) {
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += (int64_t)gridDim.x * kBlock) {
+    const int64_t t = (int64_t)(sorted_uniform(z, M, i) * kTwo62);
+    const int64_t a = count_below(cum, N, t);
+    ancestors[i] = (int32_t)(a < N - 1 ? a : N - 1);
+  }
+}
+
+// resampling.py::residual, the split: prod_j = wf_j * M exactly (at most 86 bits), cnt_j = prod_j >> 62 copies for
+// certain, rem_j = (prod_j mod 2^62) >> 24 the weight of particle j in the multinomial draw of the rest.
+__global__ void __launch_bounds__(kBlock)
+k_residual_split(int64_t N, int64_t M, const float* __restrict__ w, int64_t* __restrict__ cnt,
+                 int64_t* __restrict__ rem) {
+  for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < N; j += (int64_t)gridDim.x * kBlock) {
+    const uint64_t wf = (uint64_t)scan_item(w, j);
+    const uint64_t lo = wf * (uint64_t)M, hi = __umul64hi(wf, (uint64_t)M);
+    cnt[j] = (int64_t)((hi << 2) | (lo >> 62));
+    rem[j] = (int64_t)((lo & kMask62) >> 24);
+  }
+}
+
+// Position i < S = Ccnt[N - 1] is the i-th entry of repeat(arange(N), cnt): #{j : Ccnt_j <= i}.  Position i >= S is
+// entry perm[i] of the multinomial sample of the remainders: min(N - 1, #{j : Crem_j < (int64)(pos_p * Crem[N - 1])}).
+__global__ void __launch_bounds__(kBlock)
+k_resample_residual(int64_t N, int64_t M, const int64_t* __restrict__ ccnt, const int64_t* __restrict__ crem,
+                    const int64_t* __restrict__ z, const int32_t* __restrict__ perm,
+                    int32_t* __restrict__ ancestors) {
+  const int64_t S = ccnt[N - 1];
+  const double rem_total = (double)crem[N - 1];
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += (int64_t)gridDim.x * kBlock) {
+    int64_t a;
+    if (i < S) {
+      a = count_below(ccnt, N, i + 1);
+    } else {
+      int64_t p = perm ? (int64_t)perm[i] : i;
+      p = p < 0 ? 0 : (p > M - 1 ? M - 1 : p);  // the read of z stays in bounds whatever perm holds
+      a = count_below(crem, N, (int64_t)(sorted_uniform(z, M, p) * rem_total));
+    }
+    ancestors[i] = (int32_t)(a < N - 1 ? a : N - 1);
+  }
+}
+
+// out[row0 + i * row_stride, :] = x[i, :], one wavefront per source row (the mapping of k_gather)
+template <int VEC>
+__global__ void __launch_bounds__(kBlock)
+k_scatter_rows(int64_t M, int64_t D, const float* __restrict__ x, int64_t row0, int64_t row_stride,
+               float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t r = wave_row0(); r < M; r += wave_row_stride()) {
+    const float* src = x + r * D;
+    float* dst = out + (row0 + r * row_stride) * D;
+    for (int64_t j = (int64_t)lane * VEC; j < D; j += 64 * VEC) {
+      if constexpr (VEC == 4) st4(dst + j, ld4(src + j));
+      else dst[j] = src[j];
+    }
+  }
+}
+
+// ---- column moments of the particles -----------------------------------------------------------------------
+constexpr int kMomTile = 256;  // rows per workgroup: fixed, so the partials depend on (N, D) alone
+
+// columns per workgroup: at most 64 (one wavefront across a row piece of 256 bytes), so that wide particles spread
+// over D / 64 workgroups per tile and every column still has 4 row groups
+__host__ __device__ inline int mom_cols(int64_t D) { return D >= 64 ? 64 : (D >= 16 ? 16 : 4); }
+
+// Adds the kBlock / cw row groups of a column in a fixed order; every thread of the column gets the total.
+__device__ __forceinline__ double column_total(double v, double* sh, int cw) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  double t = 0.0;
+  for (int k = threadIdx.x % cw; k < kBlock; k += cw) t += sh[k];
+  __syncthreads();
+  return t;
+}
+
+// Workgroup (tile, column block): cw consecutive columns (consecutive threads: reads coalesced along D) by
+// kBlock / cw row groups.  part[(tile * D + j) * 2 + {0, 1}] = the tile's mean of column j and its sum of squared
+// deviations from that mean, fp64.
+__global__ void __launch_bounds__(kBlock)
+k_moments_tile(int64_t N, int64_t D, int cw, const float* __restrict__ x, double* __restrict__ part) {
+  __shared__ double sh[kBlock];
+  const int tx = threadIdx.x % cw, ty = threadIdx.x / cw, groups = kBlock / cw;
+  const int64_t j = (int64_t)blockIdx.y * cw + tx;
+  const int64_t r0 = (int64_t)blockIdx.x * kMomTile;
+  const int64_t r1 = r0 + kMomTile < N ? r0 + kMomTile : N;
+  double s = 0.0;
+  if (j < D)
+    for (int64_t r = r0 + ty; r < r1; r += groups) s += (double)x[r * D + j];
+  const double mean = column_total(s, sh, cw) / (double)(r1 - r0);
+  double q = 0.0;
+  if (j < D)
+    for (int64_t r = r0 + ty; r < r1; r += groups) {
+      const double d = (double)x[r * D + j] - mean;
+      q += d * d;
+    }
+  q = column_total(q, sh, cw);
+  if (ty == 0 && j < D) {
+    part[(blockIdx.x * D + j) * 2] = mean;
+    part[(blockIdx.x * D + j) * 2 + 1] = q;
+  }
+}
+
+// One thread per column merges the tiles in order (Chan et al.): mean and M2 of the union of two sets.  The fp64
+// results stay in `total` (mean (D,), then M2 (D,)) for callers that centre the rows.
+__global__ void __launch_bounds__(kBlock)
+k_moments_combine(int64_t N, int64_t D, int64_t tiles, const double* __restrict__ part, double* __restrict__ total,
+                  float* __restrict__ mean_out, float* __restrict__ std_out) {
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (j >= D) return;
+  double n = 0.0, mean = 0.0, m2 = 0.0;
+  for (int64_t t = 0; t < tiles; ++t) {
+    const int64_t r0 = t * kMomTile;
+    const double nb = (double)((r0 + kMomTile < N ? r0 + kMomTile : N) - r0);
+    const double delta = part[(t * D + j) * 2] - mean, nn = n + nb;
+    mean += delta * (nb / nn);
+    m2 += part[(t * D + j) * 2 + 1] + delta * delta * (n * nb / nn);
+    n = nn;
+  }
+  total[j] = mean;
+  total[D + j] = m2;
+  mean_out[j] = (float)mean;
+  if (std_out) std_out[j] = (float)sqrt(m2 / (double)N);
+}
+
 unsigned flat_grid(int64_t n_items) {
   const int64_t b = (n_items + kBlock - 1) / kBlock;
   return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
 }
 
 int64_t n_tiles(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
+
+// int64 words of an n-item scan: the items, then the tile sums of every level
+int64_t scan_words(int64_t n) {
+  int64_t words = n;
+  for (int64_t m = n; n_tiles(m) > 1; m = n_tiles(m)) words += n_tiles(m);
+  return words;
+}
+
+constexpr int64_t kMaxMomentCols = (int64_t)1 << 20;
+int64_t mom_tiles(int64_t N) { return (N + kMomTile - 1) / kMomTile; }
 
 // Inclusive scan of n items into out; ws holds the tile sums of this level and of every level above it.
 template <typename In>
@@ -371,6 +542,74 @@ int bjx_smc_resample(void* stream, uint32_t key0, uint32_t key1, int32_t stratif
     hipLaunchKernelGGL(k_resample<false>, grid, block, 0, s, key, N, num_samples, (const int64_t*)workspace,
                        ancestors_out);
   return bjx_check_launch("bjx_smc_resample");
+}
+
+int64_t bjx_smc_resample_sorted_workspace_bytes(int64_t N, int64_t num_samples) {
+  if (N < 1 || N > kMaxParticles || num_samples < 0 || num_samples > kMaxParticles) return 0;
+  // two scans over the particles (cumulative weights, or copies and remainders), one over the exponentials
+  return (2 * scan_words(N) + scan_words(num_samples + 1)) * (int64_t)sizeof(int64_t);
+}
+
+int bjx_smc_resample_sorted(void* stream, uint32_t key0, uint32_t key1, int32_t mode, int64_t N,
+                            int64_t num_samples, const float* weights, const int32_t* perm, int64_t* workspace,
+                            int32_t* ancestors_out) {
+  BJX_CHECK_ARG(N >= 1 && N <= kMaxParticles && num_samples >= 0 && num_samples <= kMaxParticles &&
+                    (mode == BJX_SMC_MULTINOMIAL || mode == BJX_SMC_RESIDUAL),
+                "bjx_smc_resample_sorted: bad sizes");
+  if (num_samples == 0) return 0;
+  BJX_CHECK_ARG(weights && workspace && ancestors_out, "bjx_smc_resample_sorted: null pointer");
+  const hipStream_t s = (hipStream_t)stream;
+  const int64_t M = num_samples, wn = scan_words(N);
+  int64_t* a = workspace;           // C, or Ccnt
+  int64_t* b = workspace + wn;      // Crem
+  int64_t* z = workspace + 2 * wn;  // Z, M + 1 items
+  const dim3 block(kBlock);
+  hipLaunchKernelGGL(k_exp_fixed, dim3(flat_grid(M + 1)), block, 0, s, Key{key0, key1}, M + 1, z);
+  scan_level<int64_t>(s, z, M + 1, z, z + M + 1);
+  if (mode == BJX_SMC_MULTINOMIAL) {
+    scan_level<float>(s, weights, N, a, a + N);
+    hipLaunchKernelGGL(k_resample_multinomial, dim3(flat_grid(M)), block, 0, s, N, M, (const int64_t*)a,
+                       (const int64_t*)z, ancestors_out);
+  } else {
+    hipLaunchKernelGGL(k_residual_split, dim3(flat_grid(N)), block, 0, s, N, M, weights, a, b);
+    scan_level<int64_t>(s, a, N, a, a + N);
+    scan_level<int64_t>(s, b, N, b, b + N);
+    hipLaunchKernelGGL(k_resample_residual, dim3(flat_grid(M)), block, 0, s, N, M, (const int64_t*)a,
+                       (const int64_t*)b, (const int64_t*)z, perm, ancestors_out);
+  }
+  return bjx_check_launch("bjx_smc_resample_sorted");
+}
+
+int bjx_smc_scatter_rows(void* stream, int64_t M, int64_t D, const float* x, int64_t row0, int64_t row_stride,
+                         float* out) {
+  BJX_CHECK_ARG(M >= 0 && D > 0 && row0 >= 0 && row_stride >= 1, "bjx_smc_scatter_rows: bad sizes");
+  if (M == 0) return 0;
+  BJX_CHECK_ARG(x && out, "bjx_smc_scatter_rows: null pointer");
+  BJX_CHECK_ARG(x != out, "bjx_smc_scatter_rows: out of place only");
+  BJX_LAUNCH_ROWS_VEC(bjx_vec4_ok(D, x, out), k_scatter_rows, M, stream, M, D, x, row0, row_stride, out);
+  return bjx_check_launch("bjx_smc_scatter_rows");
+}
+
+int bjx_smc_moments_tile(void) { return kMomTile; }
+
+int64_t bjx_smc_particle_moments_workspace_bytes(int64_t N, int64_t D) {
+  if (N < 1 || N > kMaxParticles || D < 1 || D > kMaxMomentCols) return 0;
+  return (2 * mom_tiles(N) * D + 2 * D) * (int64_t)sizeof(double);  // the tiles' partials, then mean and M2
+}
+
+int bjx_smc_particle_moments(void* stream, int64_t N, int64_t D, const float* x, void* workspace, float* mean_out,
+                             float* std_out) {
+  BJX_CHECK_ARG(N >= 1 && N <= kMaxParticles && D >= 1 && D <= kMaxMomentCols,
+                "bjx_smc_particle_moments: bad sizes");
+  BJX_CHECK_ARG(x && workspace && mean_out, "bjx_smc_particle_moments: null pointer");
+  const int64_t tiles = mom_tiles(N);
+  const int cw = mom_cols(D);
+  double* part = (double*)workspace;
+  hipLaunchKernelGGL(k_moments_tile, dim3((unsigned)tiles, (unsigned)((D + cw - 1) / cw)), dim3(kBlock), 0,
+                     (hipStream_t)stream, N, D, cw, x, part);
+  hipLaunchKernelGGL(k_moments_combine, dim3(flat_grid(D)), dim3(kBlock), 0, (hipStream_t)stream, N, D, tiles,
+                     (const double*)part, part + 2 * tiles * D, mean_out, std_out);
+  return bjx_check_launch("bjx_smc_particle_moments");
 }
 
 int bjx_smc_gather(void* stream, int64_t N, int64_t num_samples, int64_t D, const float* x,

@@ -116,18 +116,7 @@ def base(num_folds: int = 4, step_size_multiplier: float = 0.5, damping_slowdown
     return init, update
 
 
-def _permutation(rng_key, n: int) -> np.ndarray:
-    """``jax.random.permutation(key, n)`` (jax/_src/random.py::_shuffle): ceil(3 ln n / ln(2^32 - 1))
-    rounds of a stable sort by fresh 32-bit keys, ``key, subkey = split(key)`` per round."""
-    x = np.arange(n, dtype=np.int64)
-    rounds = int(np.ceil(3 * np.log(max(1, n)) / np.log(float(2**32 - 1))))
-    key = rng_key
-    for _ in range(rounds):
-        key, sub = bjx_random.split(key, 2)
-        words = bjx_random.split(sub, n)  # random_bits(sub, 32, (n,))[i] = xor of the words of child i
-        bits = words[:, 0] ^ words[:, 1]
-        x = x[np.argsort(bits, kind="stable")]
-    return x
+_permutation = bjx_random.permutation  # jax.random.permutation(key, n) on the host; shared with smc.resampling
 
 
 def meads_adaptation(logdensity_fn: Callable, num_chains: int, num_folds: int = 4,

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["key", "PRNGKey", "split", "fold_in", "uniform", "key_words", "ChainMajorKey", "key_spec", "chain_normal"]
+__all__ = ["key", "PRNGKey", "split", "fold_in", "uniform", "permutation", "key_words", "ChainMajorKey", "key_spec", "chain_normal"]
 
 
 def key(seed: int) -> np.ndarray:
@@ -62,6 +62,20 @@ def uniform(rng_key) -> np.float32:
     f = (np.array([(bits >> np.uint32(9)) | np.uint32(0x3F800000)], np.uint32).view(np.float32)[0]
          - np.float32(1.0))
     return np.float32(max(np.float32(0.0), f))
+
+
+def permutation(rng_key, n: int) -> np.ndarray:
+    """``jax.random.permutation(key, n)`` (jax/_src/random.py::_shuffle): ceil(3 ln n / ln(2^32 - 1))
+    rounds of a stable sort by fresh 32-bit keys, ``key, subkey = split(key)`` per round."""
+    x = np.arange(n, dtype=np.int64)
+    rounds = int(np.ceil(3 * np.log(max(1, n)) / np.log(float(2**32 - 1))))
+    key = rng_key
+    for _ in range(rounds):
+        key, sub = split(key, 2)
+        words = split(sub, n)  # random_bits(sub, 32, (n,))[i] = xor of the words of child i
+        bits = words[:, 0] ^ words[:, 1]
+        x = x[np.argsort(bits, kind="stable")]
+    return x
 
 
 class ChainMajorKey:

@@ -25,10 +25,13 @@ init = tempered.init
 
 
 def build_kernel(logprior_fn: Callable, loglikelihood_fn: Callable, mcmc_step_fn: Callable, mcmc_init_fn: Callable,
-                 resampling_fn: Callable, target_ess: float, root_solver: Callable = solver.dichotomy):
+                 resampling_fn: Callable, target_ess: float, root_solver: Callable = solver.dichotomy,
+                 update_strategy: Callable = base.update_and_take_last):
     """blackjax/smc/adaptive_tempered.py ``build_kernel``: ``kernel(rng_key, state, num_mcmc_steps,
-    mcmc_parameters)``.  ``root_solver(loglikelihood, target_ess, max_delta) -> delta`` works on device tensors."""
-    tempered_kernel = tempered.build_kernel(logprior_fn, loglikelihood_fn, mcmc_step_fn, mcmc_init_fn, resampling_fn)
+    mcmc_parameters)``.  ``root_solver(loglikelihood, target_ess, max_delta) -> delta`` works on device tensors.
+    The solve sees the log-likelihood of all ``N`` incoming particles whatever ``update_strategy`` resamples."""
+    tempered_kernel = tempered.build_kernel(logprior_fn, loglikelihood_fn, mcmc_step_fn, mcmc_init_fn, resampling_fn,
+                                            update_strategy)
     logdensity = tempered_kernel.tempered_logdensity
 
     def kernel(rng_key, state: tempered.TemperedSMCState, num_mcmc_steps: int, mcmc_parameters: dict):
@@ -49,10 +52,12 @@ def build_kernel(logprior_fn: Callable, loglikelihood_fn: Callable, mcmc_step_fn
 
 def as_top_level_api(logprior_fn: Callable, loglikelihood_fn: Callable, mcmc_step_fn: Callable,
                      mcmc_init_fn: Callable, mcmc_parameters: dict, resampling_fn: Callable, target_ess: float,
-                     root_solver: Callable = solver.dichotomy, num_mcmc_steps: int = 10) -> SamplingAlgorithm:
-    """blackjax/smc/adaptive_tempered.py ``as_top_level_api``: ``init(particles)``, ``step(rng_key, state)``."""
+                     root_solver: Callable = solver.dichotomy, num_mcmc_steps: int = 10,
+                     update_strategy: Callable = base.update_and_take_last) -> SamplingAlgorithm:
+    """blackjax/smc/adaptive_tempered.py ``as_top_level_api``: ``init(particles)``, ``step(rng_key, state)``.
+    ``update_strategy=waste_free_smc(N, p)`` goes with ``num_mcmc_steps=None``."""
     kernel = build_kernel(logprior_fn, loglikelihood_fn, mcmc_step_fn, mcmc_init_fn, resampling_fn, target_ess,
-                          root_solver)
+                          root_solver, update_strategy)
 
     def init_fn(particles, rng_key=None):
         del rng_key

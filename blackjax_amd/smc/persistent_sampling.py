@@ -30,7 +30,9 @@ Deliberate differences from the reference:
 * A step beyond ``n_schedule`` raises ``ValueError``, and ``init`` checks ``(n_schedule + 1) * N <= 2**24``
   (resampling positions are fp32).
 
-Out of scope: as for ``blackjax_amd.smc.tempered``, and updating ``den`` incrementally from one step to the next.
+Out of scope: as for ``blackjax_amd.smc.tempered``, waste-free moves (``smc.waste_free`` is not supported here: the
+step always resamples ``N``) and inner-kernel tuning around this sampler, and updating ``den`` incrementally from one
+step to the next.
 """
 from __future__ import annotations
 

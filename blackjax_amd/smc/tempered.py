@@ -20,9 +20,14 @@ A particle whose log-likelihood is ``-inf`` or NaN gets weight 0.  If EVERY part
 temperature moved) the weights are NaN and the increment is ``-inf``; no host check is made for it.  With
 ``lam_new == lam_old`` the weights are uniform whatever the log-likelihoods are.
 
-Out of scope: ``multinomial`` / ``residual`` resampling, partial-posteriors, pretuning and waste-free SMC (persistent
-sampling is ``blackjax_amd.smc.persistent_sampling``), inner-kernel tuning, pytrees of particles, and sharding the particles across GPUs (resampling is global: there is no
-``chain_offset`` here).
+``update_strategy`` decides how the resampled particles are moved and how many are resampled: ``update_and_take_last``
+(all ``N``, the last of ``num_mcmc_steps`` states kept) or ``blackjax_amd.smc.waste_free.waste_free_smc(N, p)``
+(``N / p`` ancestors, every state kept; ``SMCInfo.ancestors`` is then ``(N / p,)``).  The parameters of the move can
+be re-estimated between temperatures with ``blackjax_amd.smc.inner_kernel_tuning``.
+
+Out of scope: partial-posteriors and pretuning (persistent sampling is ``blackjax_amd.smc.persistent_sampling``),
+pytrees of particles, and sharding the particles across GPUs (resampling is global: there is no ``chain_offset``
+here).
 """
 from __future__ import annotations
 
@@ -120,10 +125,10 @@ def build_kernel(logprior_fn: Callable, loglikelihood_fn: Callable, mcmc_step_fn
         lam_new = base.device_scalar(lmbda, x.device)
         keys = split(rng_key, 2)
         updating_key, resampling_key = keys[0], keys[1]
-        ancestors = resample(resampling_key, w, n)
+        update, num_resampled = update_strategy(mcmc_init_fn, tempered, mcmc_step_fn, num_mcmc_steps, n)
+        ancestors = resample(resampling_key, w, num_resampled)
         x = base.gather(x, ancestors)
         tempered.set_temperature(lam_old)
-        update, _ = update_strategy(mcmc_init_fn, tempered, mcmc_step_fn, num_mcmc_steps, n)
         x, update_info = update(updating_key, x, mcmc_parameters)
         weights, increment, lam = base.reweight(tempered.loglikelihood(x), lam_old, lam_new)
         return TemperedSMCState(x, weights, lam), base.SMCInfo(ancestors, increment, update_info)
@@ -134,9 +139,11 @@ def build_kernel(logprior_fn: Callable, loglikelihood_fn: Callable, mcmc_step_fn
 
 def as_top_level_api(logprior_fn: Callable, loglikelihood_fn: Callable, mcmc_step_fn: Callable,
                      mcmc_init_fn: Callable, mcmc_parameters: dict, resampling_fn: Callable,
-                     num_mcmc_steps: int = 10) -> SamplingAlgorithm:
-    """blackjax/smc/tempered.py ``as_top_level_api``: ``init(particles)``, ``step(rng_key, state, lmbda)``."""
-    kernel = build_kernel(logprior_fn, loglikelihood_fn, mcmc_step_fn, mcmc_init_fn, resampling_fn)
+                     num_mcmc_steps: int = 10,
+                     update_strategy: Callable = base.update_and_take_last) -> SamplingAlgorithm:
+    """blackjax/smc/tempered.py ``as_top_level_api``: ``init(particles)``, ``step(rng_key, state, lmbda)``.
+    ``update_strategy=waste_free_smc(N, p)`` goes with ``num_mcmc_steps=None``."""
+    kernel = build_kernel(logprior_fn, loglikelihood_fn, mcmc_step_fn, mcmc_init_fn, resampling_fn, update_strategy)
 
     def init_fn(particles, rng_key=None):
         del rng_key

@@ -760,6 +760,49 @@ int bjx_smc_log_ess(void* stream, int64_t N, const float* log_weights, float* lo
 int bjx_smc_ess_solve(void* stream, int64_t N, const float* loglik, float target_ess, const float* max_delta,
                       const float* lam_old, float* delta_out, float* lam_new_out);
 
+/* Multinomial and residual resampling.  Integer sums only, as above: the ancestors do not depend on the tiling.
+ * Sorted uniforms (resampling.py::_sorted_uniforms, z = cumsum(-log(uniform(key, (M + 1,)))), z[:-1] / z[-1]) for
+ * M = num_samples positions:
+ *   u_k  = uniform(key, (M + 1,))[k]                                      (fp32, as the stratified scheme draws it)
+ *   e_k  = -log1p(-u_k), correctly rounded to fp32 (bjx_log1p.h).  1 - u is as uniform as u and -u lies in (-1, 0]:
+ *          e_k < 16 is finite even for a draw of exactly 0, which gives inf in the reference (a deliberate deviation)
+ *   ef_k = (int64) floor((double) e_k * 2^24) ; Z = inclusive prefix sum (below 2^53: every conversion is exact)
+ *   pos_i = (double) Z_i / (double) max(Z_M, 1)                           (i < M; non-decreasing)
+ * mode BJX_SMC_MULTINOMIAL:  ancestors_out[i] = min(N - 1, #{j : C_j < (int64)(pos_i * 2^62)}), C as above.
+ * mode BJX_SMC_RESIDUAL:  prod_j = wf_j * M exactly (86 bits) ; cnt_j = prod_j >> 62 ; rem_j = (prod_j mod 2^62) >> 24 ;
+ *   Ccnt, Crem = their inclusive prefix sums ; S = Ccnt[N - 1] (never read by the host)
+ *   i <  S:  ancestors_out[i] = min(N - 1, #{j : Ccnt_j <= i})                        (repeat(arange(N), cnt)[i])
+ *   i >= S:  p = perm[i] (i when perm is null; clamped to [0, M)) ;
+ *            ancestors_out[i] = min(N - 1, #{j : Crem_j < (int64)(pos_p * (double) Crem[N - 1])})
+ *   The reference splits its key in two: (key0, key1) here is the FIRST half (the multinomial draw of the remainders);
+ *   perm is jax.random.permutation(second half, M), which depends on the key alone and is formed by the caller.
+ * 1 <= N <= 2^24, num_samples <= 2^24.  workspace: bjx_smc_resample_sorted_workspace_bytes(N, num_samples) bytes (0 for
+ * arguments out of range), 8-byte aligned.  num_samples == 0 is a no-op.
+ * Replaces: smc/resampling.py::multinomial, residual, _sorted_uniforms. */
+#define BJX_SMC_MULTINOMIAL 0
+#define BJX_SMC_RESIDUAL 1
+int64_t bjx_smc_resample_sorted_workspace_bytes(int64_t N, int64_t num_samples);
+int bjx_smc_resample_sorted(void* stream, uint32_t key0, uint32_t key1, int32_t mode, int64_t N,
+                            int64_t num_samples, const float* weights, const int32_t* perm, int64_t* workspace,
+                            int32_t* ancestors_out);
+/* out[row0 + i * row_stride, :] = x[i, :] for i < M, x (M, D); every other row of out keeps its bytes.  The caller
+ * guarantees that out has at least row0 + (M - 1) * row_stride + 1 rows.  One wavefront per row; 16-byte accesses when
+ * D % 4 == 0 and both arrays are 16-byte aligned, as bjx_smc_gather.  row0 >= 0, row_stride >= 1, out of place.
+ * Replaces: smc/waste_free.py::update_waste_free (the reshape of the scanned states and its concatenation). */
+int bjx_smc_scatter_rows(void* stream, int64_t M, int64_t D, const float* x, int64_t row0, int64_t row_stride,
+                         float* out);
+/* Column means and standard deviations (ddof 0) of x (N, D), fp64 accumulators, each result rounded once.  One
+ * workgroup per tile of bjx_smc_moments_tile() rows and block of columns writes the tile's (mean, sum of squared
+ * deviations from it); a second launch merges the tiles in order (Chan et al.).  Launch-separated, and the tiling
+ * depends on (N, D) alone: the result is reproducible bit for bit.  std_out may be null.  workspace:
+ * bjx_smc_particle_moments_workspace_bytes(N, D) bytes (0 for 1 <= N <= 2^24, 1 <= D <= 2^20 violated), 8-byte aligned;
+ * on return its last 2 D doubles hold the fp64 means and the fp64 sums of squared deviations.
+ * Replaces: smc/tuning/from_particles.py::particles_means, particles_stds. */
+int bjx_smc_moments_tile(void);
+int64_t bjx_smc_particle_moments_workspace_bytes(int64_t N, int64_t D);
+int bjx_smc_particle_moments(void* stream, int64_t N, int64_t D, const float* x, void* workspace, float* mean_out,
+                             float* std_out);
+
 /* Persistent sampling (blackjax.persistent_sampling_smc / adaptive_persistent_sampling_smc).  Iteration i weighs
  * the P = i * N particles of ALL earlier iterations against the mixture of their tempered targets:
  *   den_j = logsumexp_{s < n_terms}(a_sj - log_Z[s]) - log(n_terms), a_sj = schedule[s] * loglik[j] in fp32 (exactly 0
