@@ -28,6 +28,12 @@ static inline int bjx_check_launch(const char* what) {
 // Row-per-wave kernels: one row per wave (>> 256 CUs worth of workgroups); grid-stride only
 // beyond 65536 workgroups (BJX_MAX_BLOCKS overrides).
 unsigned bjx_row_grid(int64_t n_rows, int waves_per_block);
+// Grid-stride kernels over n_items flat items, `block` threads per workgroup: ceil(n_items / block) clamped to
+// [1, 65536].
+static inline unsigned bjx_flat_grid(int64_t n_items, int block) {
+  const int64_t b = (n_items + block - 1) / block;
+  return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
+}
 
 // 16-byte vector path is legal when D % 4 == 0 and every non-null pointer is 16-B aligned.
 static inline bool bjx_vec4_ptr_ok(const void* p) { return p == nullptr || ((uintptr_t)p & 15u) == 0; }

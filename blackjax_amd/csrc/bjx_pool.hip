@@ -805,7 +805,7 @@ __global__ __launch_bounds__(256) void k_pool_center(int64_t N, int64_t D, const
 
 __global__ void k_halton_steps(int64_t N, const int32_t* __restrict__ arg, int max_bits, float ja, float jb,
                                float num_leapfrog, int32_t* __restrict__ steps) {
-  // grid-stride: flat_grid caps the launch at 65 536 workgroups (16.7 M chains per sweep)
+  // grid-stride: bjx_flat_grid caps the launch at 65 536 workgroups (16.7 M chains per sweep)
   for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < N;
        n += (int64_t)gridDim.x * blockDim.x) {
     const uint32_t i = (uint32_t)arg[n] + 1u;
@@ -815,13 +815,6 @@ __global__ void k_halton_steps(int64_t N, const int32_t* __restrict__ arg, int m
     const float jitter = h * ja + jb;
     steps[n] = (int32_t)ceilf(jitter * num_leapfrog);
   }
-}
-
-inline unsigned flat_grid(int64_t n, int block) {
-  int64_t b = (n + block - 1) / block;
-  if (b < 1) b = 1;
-  if (b > 65536) b = 65536;
-  return (unsigned)b;
 }
 
 }  // namespace
@@ -933,7 +926,7 @@ int bjx_chees_means(hipStream_t stream, int64_t D, const double* stats, const fl
   BJX_CHECK_ARG(D >= 0, "bjx_chees_means: negative size");
   if (D == 0) return 0;
   BJX_CHECK_ARG(stats && proposals_mean && initials_mean, "bjx_chees_means: null pointer");
-  hipLaunchKernelGGL(k_chees_means, dim3(flat_grid(D, 256)), dim3(256), 0, stream, D, stats, imm,
+  hipLaunchKernelGGL(k_chees_means, dim3(bjx_flat_grid(D, 256)), dim3(256), 0, stream, D, stats, imm,
                      proposals_mean, initials_mean, inv_sqrt_imm);
   return bjx_check_launch("bjx_chees_means");
 }
@@ -1022,7 +1015,7 @@ int bjx_pool_mean(hipStream_t stream, int64_t D, const double* sum, double count
   BJX_CHECK_ARG(D >= 0, "bjx_pool_mean: negative size");
   if (D == 0) return 0;
   BJX_CHECK_ARG(sum && mean, "bjx_pool_mean: null pointer");
-  hipLaunchKernelGGL(k_pool_mean, dim3(flat_grid(D, 256)), dim3(256), 0, stream, D, sum, count, mean);
+  hipLaunchKernelGGL(k_pool_mean, dim3(bjx_flat_grid(D, 256)), dim3(256), 0, stream, D, sum, count, mean);
   return bjx_check_launch("bjx_pool_mean");
 }
 
@@ -1032,7 +1025,7 @@ int bjx_pool_merge_diag(hipStream_t stream, int64_t D, float n_a, float n_b, con
   if (D == 0) return 0;
   BJX_CHECK_ARG(mean_b && m2_b_sum && mean && m2, "bjx_pool_merge_diag: null pointer");
   BJX_CHECK_ARG(n_a + n_b > 0.0f, "bjx_pool_merge_diag: empty merge");
-  hipLaunchKernelGGL(k_pool_merge_diag, dim3(flat_grid(D, 256)), dim3(256), 0, stream, D, n_a, n_b,
+  hipLaunchKernelGGL(k_pool_merge_diag, dim3(bjx_flat_grid(D, 256)), dim3(256), 0, stream, D, n_a, n_b,
                      mean_b, m2_b_sum, mean, m2);
   return bjx_check_launch("bjx_pool_merge_diag");
 }
@@ -1041,7 +1034,7 @@ int bjx_pool_final_diag(hipStream_t stream, int64_t D, float count, const float*
   BJX_CHECK_ARG(D >= 0, "bjx_pool_final_diag: negative size");
   if (D == 0) return 0;
   BJX_CHECK_ARG(m2 && imm, "bjx_pool_final_diag: null pointer");
-  hipLaunchKernelGGL(k_pool_final_diag, dim3(flat_grid(D, 256)), dim3(256), 0, stream, D, count, m2, imm);
+  hipLaunchKernelGGL(k_pool_final_diag, dim3(bjx_flat_grid(D, 256)), dim3(256), 0, stream, D, count, m2, imm);
   return bjx_check_launch("bjx_pool_final_diag");
 }
 
@@ -1051,10 +1044,10 @@ int bjx_pool_center(hipStream_t stream, int64_t N, int64_t D, const float* x, co
   if (N == 0 || D == 0) return 0;
   BJX_CHECK_ARG(x && center && centered, "bjx_pool_center: null pointer");
   if (bjx_vec4_ok(D, x, center, centered))
-    hipLaunchKernelGGL(k_pool_center<4>, dim3(flat_grid(N * (D / 4), 256)), dim3(256), 0, stream, N, D,
+    hipLaunchKernelGGL(k_pool_center<4>, dim3(bjx_flat_grid(N * (D / 4), 256)), dim3(256), 0, stream, N, D,
                        x, center, centered);
   else
-    hipLaunchKernelGGL(k_pool_center<1>, dim3(flat_grid(N * D, 256)), dim3(256), 0, stream, N, D, x,
+    hipLaunchKernelGGL(k_pool_center<1>, dim3(bjx_flat_grid(N * D, 256)), dim3(256), 0, stream, N, D, x,
                        center, centered);
   return bjx_check_launch("bjx_pool_center");
 }
@@ -1067,7 +1060,7 @@ int bjx_halton_steps(hipStream_t stream, int64_t N, const int32_t* arg, int32_t 
                 "bjx_halton_steps: max_bits must be less than bit width of dtype int32 (32)");
   if (N == 0) return 0;
   BJX_CHECK_ARG(arg && steps, "bjx_halton_steps: null pointer");
-  hipLaunchKernelGGL(k_halton_steps, dim3(flat_grid(N, 256)), dim3(256), 0, stream, N, arg, (int)max_bits,
+  hipLaunchKernelGGL(k_halton_steps, dim3(bjx_flat_grid(N, 256)), dim3(256), 0, stream, N, arg, (int)max_bits,
                      jitter_amount, jitter_offset, num_leapfrog_steps, steps);
   return bjx_check_launch("bjx_halton_steps");
 }

@@ -10,25 +10,23 @@
 // is the same whatever the tiling, and the ancestor search compares integers.  The scan is launch-separated (tile
 // sums -> scan of the tile sums -> apply): no workgroup ever waits on another.  The log-sum-exp reweighting and the
 // ESS bisection are one workgroup each, looping over the (N,) log-likelihoods with fp64 sums: the number of
-// launches does not depend on the data and nothing is read back by the host.
+// launches does not depend on the data and nothing is read back by the host.  Which log-weights count, the order
+// of a workgroup's sums and the tile of 1024 items are bjx_smc_dev.h's, shared with bjx_smc_persistent.hip.
 #include <math.h>
 
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
 #include "bjx_rows.h"
+#include "bjx_smc_dev.h"
 
 using namespace bjx;
 
 namespace {
 
-constexpr int kScanItems = 4;                    // consecutive items per thread
-constexpr int kScanTile = kBlock * kScanItems;   // 1024 items per workgroup
 constexpr int kRedBlock = 1024;                  // the one workgroup of the reweight / ESS kernels
 constexpr int kRedWaves = kRedBlock / BJX_WAVE;
-constexpr int64_t kMaxParticles = (int64_t)1 << 24;  // positions are formed in fp32
 constexpr double kTwo62 = 4611686018427387904.0;
-constexpr int kHalvings = 30;
 
 // wf = (int64) floor((double) w * 2^62); anything that is not a weight in (0, 1] is clamped so that the sum of at
 // most 2^24 of them cannot leave int64 by more than a wrap the search survives (ancestors are clipped to [0, N)).
@@ -65,10 +63,10 @@ __device__ __forceinline__ int64_t block_scan_inclusive(int64_t v, int64_t* sh, 
 template <typename In>
 __global__ void __launch_bounds__(kBlock) k_tile_sums(const In* in, int64_t n, int64_t* sums) {
   __shared__ int64_t sh[kWavesPerBlock];
-  const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
+  const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kSmcItems;
   int64_t s = 0;
 #pragma unroll
-  for (int e = 0; e < kScanItems; ++e)
+  for (int e = 0; e < kSmcItems; ++e)
     if (i0 + e < n) s += scan_item(in, i0 + e);
   int64_t total;
   block_scan_inclusive(s, sh, &total);
@@ -81,11 +79,11 @@ template <typename In>
 __global__ void __launch_bounds__(kBlock) k_tile_scan(const In* in, int64_t n, const int64_t* tile_offsets,
                                                       int64_t* out) {
   __shared__ int64_t sh[kWavesPerBlock];
-  const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kScanItems;
-  int64_t v[kScanItems];
+  const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kSmcItems;
+  int64_t v[kSmcItems];
   int64_t s = 0;
 #pragma unroll
-  for (int e = 0; e < kScanItems; ++e) {
+  for (int e = 0; e < kSmcItems; ++e) {
     v[e] = (i0 + e < n) ? scan_item(in, i0 + e) : 0;
     s += v[e];
     v[e] = s;
@@ -94,8 +92,25 @@ __global__ void __launch_bounds__(kBlock) k_tile_scan(const In* in, int64_t n, c
   const int64_t incl = block_scan_inclusive(s, sh, &total);
   const int64_t base = (incl - s) + ((tile_offsets && blockIdx.x > 0) ? tile_offsets[blockIdx.x - 1] : 0);
 #pragma unroll
-  for (int e = 0; e < kScanItems; ++e)
+  for (int e = 0; e < kSmcItems; ++e)
     if (i0 + e < n) out[i0 + e] = base + v[e];
+}
+
+// #{j < N : c_j < t}
+__device__ __forceinline__ int64_t count_below(const int64_t* __restrict__ c, int64_t N, int64_t t) {
+  int64_t lo = 0, hi = N;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (c[mid] < t) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// min(N - 1, #{j : c_j < t}): searchsorted(c, t) and the reference's clip, so an ancestor is always in [0, N)
+__device__ __forceinline__ int32_t ancestor_below(const int64_t* __restrict__ c, int64_t N, int64_t t) {
+  const int64_t a = count_below(c, N, t);
+  return (int32_t)(a < N - 1 ? a : N - 1);
 }
 
 // resampling.py::systematic / stratified: pos_i = (i + u_i) / M in fp32, u_i = uniform(key, ()) for every i
@@ -108,40 +123,49 @@ k_resample(Key key, int64_t N, int64_t M, const int64_t* __restrict__ cum, int32
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += (int64_t)gridDim.x * kBlock) {
     const float u = STRATIFIED ? fmaxf(0.0f, unit_float(key_bits32(key, (uint64_t)i))) : u_sys;
     const float pos = ((float)i + u) / (float)M;
-    const int64_t t = (int64_t)((double)pos * kTwo62);
-    int64_t lo = 0, hi = N;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (cum[mid] < t) lo = mid + 1;
-      else hi = mid;
-    }
-    ancestors[i] = (int32_t)(lo < N - 1 ? lo : N - 1);
+    ancestors[i] = ancestor_below(cum, N, (int64_t)((double)pos * kTwo62));
   }
 }
 
-// out[i, :] = x[ancestors[i], :], one wavefront per output row, 16 bytes (VEC = 4) or 4 bytes per lane.  An index
-// outside [0, N) is clamped: the launch stays inside x whatever it is given.
+// One row copied by the row's wavefront, 16 bytes (VEC = 4) or 4 bytes per lane
+template <int VEC>
+__device__ __forceinline__ void copy_row(float* __restrict__ dst, const float* __restrict__ src, int64_t D) {
+  for (int64_t j = (int64_t)(threadIdx.x & 63) * VEC; j < D; j += 64 * VEC) {
+    if constexpr (VEC == 4) st4(dst + j, ld4(src + j));
+    else dst[j] = src[j];
+  }
+}
+
+// out[i, :] = x[ancestors[i], :], one wavefront per output row.  An index outside [0, N) is clamped: the launch
+// stays inside x whatever it is given.
 template <int VEC>
 __global__ void __launch_bounds__(kBlock)
 k_gather(int64_t N, int64_t M, int64_t D, const float* __restrict__ x, const int32_t* __restrict__ ancestors,
          float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t stride = (int64_t)gridDim.x * kWavesPerBlock;
-  for (int64_t r = (int64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); r < M; r += stride) {
+  for (int64_t r = wave_row0(); r < M; r += wave_row_stride()) {
     int64_t a = ancestors[r];
     a = a < 0 ? 0 : (a > N - 1 ? N - 1 : a);
-    const float* src = x + a * D;
-    float* dst = out + r * D;
-    for (int64_t j = (int64_t)lane * VEC; j < D; j += 64 * VEC) {
-      if constexpr (VEC == 4) st4(dst + j, ld4(src + j));
-      else dst[j] = src[j];
-    }
+    copy_row<VEC>(out + r * D, x + a * D, D);
   }
 }
 
 // tempered.py::tempered_logposterior_fn and its gradient: lp + lam * ll and gp + lam * gl, the product rounded
-// before the sum (no fmaf: NumPy reproduces both bit for bit).  lam is read from device memory, so one recorded
-// or traced launch serves every temperature.
+// before the sum (no fmaf: NumPy reproduces both bit for bit).
+__device__ __forceinline__ float tempered_sum(float p, float lam, float l) {
+  const float t = lam * l;
+  return p + t;
+}
+
+// lp_out = lp + lam * ll over (N,), grid-stride: the one form of the value, so a value-only sampler (random walk)
+// and a gradient sampler see the same tempered log-density bit for bit
+__device__ __forceinline__ void temper_values(int64_t N, float lam, const float* __restrict__ lp,
+                                              const float* __restrict__ ll, float* __restrict__ lp_out) {
+  const int64_t nthr = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += nthr)
+    lp_out[i] = tempered_sum(lp[i], lam, ll[i]);
+}
+
+// Value and gradient.  lam is read from device memory, so one recorded or traced launch serves every temperature.
 template <int VEC>
 __global__ void __launch_bounds__(kBlock)
 k_temper(int64_t N, int64_t D, const float* __restrict__ lam_p, const float* __restrict__ lp,
@@ -153,60 +177,50 @@ k_temper(int64_t N, int64_t D, const float* __restrict__ lam_p, const float* __r
   for (int64_t i = tid * VEC; i < total; i += nthr * VEC) {
     if constexpr (VEC == 4) {
       const F4 a = ld4(gp + i), b = ld4(gl + i);
-      const float tx = lam * b.x, ty = lam * b.y, tz = lam * b.z, tw = lam * b.w;
-      st4(g_out + i, F4{a.x + tx, a.y + ty, a.z + tz, a.w + tw});
+      st4(g_out + i, F4{tempered_sum(a.x, lam, b.x), tempered_sum(a.y, lam, b.y), tempered_sum(a.z, lam, b.z),
+                        tempered_sum(a.w, lam, b.w)});
     } else {
-      const float t = lam * gl[i];
-      g_out[i] = gp[i] + t;
+      g_out[i] = tempered_sum(gp[i], lam, gl[i]);
     }
   }
-  for (int64_t i = tid; i < N; i += nthr) {
-    const float t = lam * ll[i];
-    lp_out[i] = lp[i] + t;
-  }
+  temper_values(N, lam, lp, ll, lp_out);
 }
 
-// The value alone: lp + lam * ll, the product rounded before the sum exactly as k_temper forms lp_out, so a value-only
-// sampler (random walk) and a gradient sampler see the same tempered log-density bit for bit.
+// The value alone
 __global__ void __launch_bounds__(kBlock)
 k_temper_value(int64_t N, const float* __restrict__ lam_p, const float* __restrict__ lp,
                const float* __restrict__ ll, float* __restrict__ lp_out) {
-  const float lam = *lam_p;
-  const int64_t nthr = (int64_t)gridDim.x * kBlock;
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < N; i += nthr) {
-    const float t = lam * ll[i];
-    lp_out[i] = lp[i] + t;
-  }
+  temper_values(N, *lam_p, lp, ll, lp_out);
 }
 
 // ---- one-workgroup reductions over (N,) -------------------------------------------------------------------
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int k = 0; k < kRedWaves; ++k) t += sh[k];
-  __syncthreads();
-  return t;
+// lw(j) is the log-weight of item j; which entries count, and the order of the sums, are bjx_smc_dev.h's.
+// The maximum over the entries that count; -inf when none does.
+template <class LogWeight>
+__device__ __forceinline__ float max_counted(int64_t N, LogWeight lw, float* sh) {
+  float m = -__builtin_inff();
+  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
+    const float v = lw(j);
+    if (lw_counts(v)) m = fmaxf(m, v);
+  }
+  return block_max<kRedWaves>(m, sh);
 }
 
-__device__ __forceinline__ float block_max(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = sh[0];
-#pragma unroll
-  for (int k = 1; k < kRedWaves; ++k) t = fmaxf(t, sh[k]);
-  __syncthreads();
-  return t;
+// S_k = sum exp(k (lw - m)) over the entries that count, k = 1, 2; the exponential and the sums in fp64.
+template <class LogWeight>
+__device__ __forceinline__ void sums_against(int64_t N, LogWeight lw, float m, double* sh, double* S1, double* S2) {
+  double s1 = 0.0, s2 = 0.0;
+  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
+    const float v = lw(j);
+    if (lw_counts(v)) {
+      const double e = exp((double)v - (double)m);
+      s1 += e;
+      s2 += e * e;
+    }
+  }
+  *S1 = block_sum<kRedWaves>(s1, sh);
+  *S2 = block_sum<kRedWaves>(s2, sh);
 }
-
-// tempered.py::log_weights_fn: delta * loglikelihood; delta == 0 gives 0 whatever ll is (the reference's
-// nan_to_num of 0 * inf).  A NaN or -inf log-weight is a particle of weight 0 and takes no part in any sum.
-__device__ __forceinline__ float log_weight(float delta, float ll) { return delta == 0.0f ? 0.0f : delta * ll; }
-__device__ __forceinline__ bool lw_counts(float lw) { return lw == lw && lw != -__builtin_inff(); }
 
 // base.py::step, the weighting: lw = (lam_new - lam_old) * ll ; lse = logsumexp(lw) ; w = exp(lw - lse) ;
 // log_likelihood_increment = lse - log N.  exp and log in fp64, the sum in fp64, each result rounded once.
@@ -218,22 +232,18 @@ k_reweight(int64_t N, const float* __restrict__ ll, const float* __restrict__ la
   __shared__ float shf[kRedWaves];
   const float lam_new = *lam_new_p;
   const float delta = lam_new - *lam_old_p;
-  float m = -__builtin_inff();
+  const auto lw_of = [&](int64_t j) { return tempered_product(delta, ll[j]); };
+  const float m = max_counted(N, lw_of, shf);
+  double s = 0.0;  // S1 alone: the shared sweep would add S2's multiply
   for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
-    const float lw = log_weight(delta, ll[j]);
-    if (lw_counts(lw)) m = fmaxf(m, lw);
-  }
-  m = block_max(m, shf);
-  double s = 0.0;
-  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
-    const float lw = log_weight(delta, ll[j]);
+    const float lw = lw_of(j);
     if (lw_counts(lw)) s += exp((double)lw - (double)m);
   }
-  s = block_sum(s, shd);
+  s = block_sum<kRedWaves>(s, shd);
   const bool none = m == -__builtin_inff();  // no particle of positive weight: weights NaN, increment -inf
   const double lse = none ? -(double)__builtin_inff() : (double)m + log(s);
   for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
-    const float lw = log_weight(delta, ll[j]);
+    const float lw = lw_of(j);
     w_out[j] = none ? __builtin_nanf("") : (lw_counts(lw) ? (float)exp((double)lw - lse) : 0.0f);
   }
   if (threadIdx.x == 0) {
@@ -247,23 +257,9 @@ __global__ void __launch_bounds__(kRedBlock)
 k_log_ess(int64_t N, const float* __restrict__ lw_in, float* __restrict__ out) {
   __shared__ double shd[kRedWaves];
   __shared__ float shf[kRedWaves];
-  float m = -__builtin_inff();
-  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
-    const float lw = lw_in[j];
-    if (lw_counts(lw)) m = fmaxf(m, lw);
-  }
-  m = block_max(m, shf);
-  double s1 = 0.0, s2 = 0.0;
-  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
-    const float lw = lw_in[j];
-    if (lw_counts(lw)) {
-      const double e = exp((double)lw - (double)m);
-      s1 += e;
-      s2 += e * e;
-    }
-  }
-  s1 = block_sum(s1, shd);
-  s2 = block_sum(s2, shd);
+  const auto lw_of = [&](int64_t j) { return lw_in[j]; };
+  double s1, s2;
+  sums_against(N, lw_of, max_counted(N, lw_of, shf), shd, &s1, &s2);
   if (threadIdx.x == 0) *out = (float)(2.0 * log(s1) - log(s2));
 }
 
@@ -280,26 +276,11 @@ k_ess_solve(int64_t N, const float* __restrict__ ll, double log_target, const fl
   __shared__ float shf[kRedWaves];
   const float lam_old = lam_old_p ? *lam_old_p : 0.0f;
   const float max_delta = max_delta_p ? *max_delta_p : 1.0f - lam_old;
-  float ll_max = -__builtin_inff();
-  for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
-    const float v = ll[j];
-    if (lw_counts(v)) ll_max = fmaxf(ll_max, v);
-  }
-  ll_max = block_max(ll_max, shf);
+  const float ll_max = max_counted(N, [&](int64_t j) { return ll[j]; }, shf);
 
   auto f = [&](float d) -> double {
-    const float m = log_weight(d, ll_max);
-    double s1 = 0.0, s2 = 0.0;
-    for (int64_t j = threadIdx.x; j < N; j += kRedBlock) {
-      const float lw = log_weight(d, ll[j]);
-      if (lw_counts(lw)) {
-        const double e = exp((double)lw - (double)m);
-        s1 += e;
-        s2 += e * e;
-      }
-    }
-    s1 = block_sum(s1, shd);
-    s2 = block_sum(s2, shd);
+    double s1, s2;
+    sums_against(N, [&](int64_t j) { return tempered_product(d, ll[j]); }, tempered_product(d, ll_max), shd, &s1, &s2);
     return 2.0 * log(s1) - log(s2) - log_target;
   };
 
@@ -344,26 +325,12 @@ __device__ __forceinline__ double sorted_uniform(const int64_t* __restrict__ z, 
   return (double)z[i] / (double)(zm > 1 ? zm : 1);
 }
 
-// #{j < N : c_j < t}
-__device__ __forceinline__ int64_t count_below(const int64_t* __restrict__ c, int64_t N, int64_t t) {
-  int64_t lo = 0, hi = N;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (c[mid] < t) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // resampling.py::multinomial: ancestor_i = min(N - 1, #{j : C_j < (int64)(pos_i * 2^62)})
 __global__ void __launch_bounds__(kBlock)
 k_resample_multinomial(int64_t N, int64_t M, const int64_t* __restrict__ cum, const int64_t* __restrict__ z,
                        int32_t* __restrict__ ancestors) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += (int64_t)gridDim.x * kBlock) {
-    const int64_t t = (int64_t)(sorted_uniform(z, M, i) * kTwo62);
-    const int64_t a = count_below(cum, N, t);
-    ancestors[i] = (int32_t)(a < N - 1 ? a : N - 1);
-  }
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += (int64_t)gridDim.x * kBlock)
+    ancestors[i] = ancestor_below(cum, N, (int64_t)(sorted_uniform(z, M, i) * kTwo62));
 }
 
 // resampling.py::residual, the split: prod_j = wf_j * M exactly (at most 86 bits), cnt_j = prod_j >> 62 copies for
@@ -388,15 +355,13 @@ k_resample_residual(int64_t N, int64_t M, const int64_t* __restrict__ ccnt, cons
   const int64_t S = ccnt[N - 1];
   const double rem_total = (double)crem[N - 1];
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < M; i += (int64_t)gridDim.x * kBlock) {
-    int64_t a;
     if (i < S) {
-      a = count_below(ccnt, N, i + 1);
+      ancestors[i] = ancestor_below(ccnt, N, i + 1);
     } else {
       int64_t p = perm ? (int64_t)perm[i] : i;
       p = p < 0 ? 0 : (p > M - 1 ? M - 1 : p);  // the read of z stays in bounds whatever perm holds
-      a = count_below(crem, N, (int64_t)(sorted_uniform(z, M, p) * rem_total));
+      ancestors[i] = ancestor_below(crem, N, (int64_t)(sorted_uniform(z, M, p) * rem_total));
     }
-    ancestors[i] = (int32_t)(a < N - 1 ? a : N - 1);
   }
 }
 
@@ -405,15 +370,8 @@ template <int VEC>
 __global__ void __launch_bounds__(kBlock)
 k_scatter_rows(int64_t M, int64_t D, const float* __restrict__ x, int64_t row0, int64_t row_stride,
                float* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  for (int64_t r = wave_row0(); r < M; r += wave_row_stride()) {
-    const float* src = x + r * D;
-    float* dst = out + (row0 + r * row_stride) * D;
-    for (int64_t j = (int64_t)lane * VEC; j < D; j += 64 * VEC) {
-      if constexpr (VEC == 4) st4(dst + j, ld4(src + j));
-      else dst[j] = src[j];
-    }
-  }
+  for (int64_t r = wave_row0(); r < M; r += wave_row_stride())
+    copy_row<VEC>(out + (row0 + r * row_stride) * D, x + r * D, D);
 }
 
 // ---- column moments of the particles -----------------------------------------------------------------------
@@ -482,12 +440,7 @@ k_moments_combine(int64_t N, int64_t D, int64_t tiles, const double* __restrict_
   if (std_out) std_out[j] = (float)sqrt(m2 / (double)N);
 }
 
-unsigned flat_grid(int64_t n_items) {
-  const int64_t b = (n_items + kBlock - 1) / kBlock;
-  return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-
-int64_t n_tiles(int64_t n) { return (n + kScanTile - 1) / kScanTile; }
+int64_t n_tiles(int64_t n) { return (n + kSmcTile - 1) / kSmcTile; }
 
 // int64 words of an n-item scan: the items, then the tile sums of every level
 int64_t scan_words(int64_t n) {
@@ -516,13 +469,11 @@ void scan_level(hipStream_t stream, const In* in, int64_t n, int64_t* out, int64
 
 extern "C" {
 
-int bjx_smc_scan_tile(void) { return kScanTile; }
+int bjx_smc_scan_tile(void) { return kSmcTile; }
 
 int64_t bjx_smc_resample_workspace_bytes(int64_t N) {
   if (N < 1 || N > kMaxParticles) return 0;
-  int64_t words = N;  // the cumulative weights, then the tile sums of every level
-  for (int64_t n = N; n_tiles(n) > 1; n = n_tiles(n)) words += n_tiles(n);
-  return words * (int64_t)sizeof(int64_t);
+  return scan_words(N) * (int64_t)sizeof(int64_t);  // the cumulative weights, then the tile sums of every level
 }
 
 int bjx_smc_resample(void* stream, uint32_t key0, uint32_t key1, int32_t stratified, int64_t N,
@@ -534,7 +485,7 @@ int bjx_smc_resample(void* stream, uint32_t key0, uint32_t key1, int32_t stratif
   const hipStream_t s = (hipStream_t)stream;
   scan_level<float>(s, weights, N, workspace, workspace + N);
   const Key key{key0, key1};
-  const dim3 grid(flat_grid(num_samples)), block(kBlock);
+  const dim3 grid(bjx_flat_grid(num_samples, kBlock)), block(kBlock);
   if (stratified)
     hipLaunchKernelGGL(k_resample<true>, grid, block, 0, s, key, N, num_samples, (const int64_t*)workspace,
                        ancestors_out);
@@ -564,17 +515,17 @@ int bjx_smc_resample_sorted(void* stream, uint32_t key0, uint32_t key1, int32_t 
   int64_t* b = workspace + wn;      // Crem
   int64_t* z = workspace + 2 * wn;  // Z, M + 1 items
   const dim3 block(kBlock);
-  hipLaunchKernelGGL(k_exp_fixed, dim3(flat_grid(M + 1)), block, 0, s, Key{key0, key1}, M + 1, z);
+  hipLaunchKernelGGL(k_exp_fixed, dim3(bjx_flat_grid(M + 1, kBlock)), block, 0, s, Key{key0, key1}, M + 1, z);
   scan_level<int64_t>(s, z, M + 1, z, z + M + 1);
   if (mode == BJX_SMC_MULTINOMIAL) {
     scan_level<float>(s, weights, N, a, a + N);
-    hipLaunchKernelGGL(k_resample_multinomial, dim3(flat_grid(M)), block, 0, s, N, M, (const int64_t*)a,
+    hipLaunchKernelGGL(k_resample_multinomial, dim3(bjx_flat_grid(M, kBlock)), block, 0, s, N, M, (const int64_t*)a,
                        (const int64_t*)z, ancestors_out);
   } else {
-    hipLaunchKernelGGL(k_residual_split, dim3(flat_grid(N)), block, 0, s, N, M, weights, a, b);
+    hipLaunchKernelGGL(k_residual_split, dim3(bjx_flat_grid(N, kBlock)), block, 0, s, N, M, weights, a, b);
     scan_level<int64_t>(s, a, N, a, a + N);
     scan_level<int64_t>(s, b, N, b, b + N);
-    hipLaunchKernelGGL(k_resample_residual, dim3(flat_grid(M)), block, 0, s, N, M, (const int64_t*)a,
+    hipLaunchKernelGGL(k_resample_residual, dim3(bjx_flat_grid(M, kBlock)), block, 0, s, N, M, (const int64_t*)a,
                        (const int64_t*)b, (const int64_t*)z, perm, ancestors_out);
   }
   return bjx_check_launch("bjx_smc_resample_sorted");
@@ -607,8 +558,8 @@ int bjx_smc_particle_moments(void* stream, int64_t N, int64_t D, const float* x,
   double* part = (double*)workspace;
   hipLaunchKernelGGL(k_moments_tile, dim3((unsigned)tiles, (unsigned)((D + cw - 1) / cw)), dim3(kBlock), 0,
                      (hipStream_t)stream, N, D, cw, x, part);
-  hipLaunchKernelGGL(k_moments_combine, dim3(flat_grid(D)), dim3(kBlock), 0, (hipStream_t)stream, N, D, tiles,
-                     (const double*)part, part + 2 * tiles * D, mean_out, std_out);
+  hipLaunchKernelGGL(k_moments_combine, dim3(bjx_flat_grid(D, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, N, D,
+                     tiles, (const double*)part, part + 2 * tiles * D, mean_out, std_out);
   return bjx_check_launch("bjx_smc_particle_moments");
 }
 
@@ -631,11 +582,11 @@ int bjx_smc_temper(void* stream, int64_t N, int64_t D, const float* lam, const f
                 "bjx_smc_temper: null pointer");
   const dim3 block(kBlock);
   if (bjx_vec4_ok(D, logprior_grad, loglik_grad, grad_out))
-    hipLaunchKernelGGL(k_temper<4>, dim3(flat_grid(N * D / 4)), block, 0, (hipStream_t)stream, N, D, lam, logprior,
-                       logprior_grad, loglik, loglik_grad, logp_out, grad_out);
+    hipLaunchKernelGGL(k_temper<4>, dim3(bjx_flat_grid(N * D / 4, kBlock)), block, 0, (hipStream_t)stream, N, D, lam,
+                       logprior, logprior_grad, loglik, loglik_grad, logp_out, grad_out);
   else
-    hipLaunchKernelGGL(k_temper<1>, dim3(flat_grid(N * D)), block, 0, (hipStream_t)stream, N, D, lam, logprior,
-                       logprior_grad, loglik, loglik_grad, logp_out, grad_out);
+    hipLaunchKernelGGL(k_temper<1>, dim3(bjx_flat_grid(N * D, kBlock)), block, 0, (hipStream_t)stream, N, D, lam,
+                       logprior, logprior_grad, loglik, loglik_grad, logp_out, grad_out);
   return bjx_check_launch("bjx_smc_temper");
 }
 
@@ -644,8 +595,8 @@ int bjx_smc_temper_value(void* stream, int64_t N, const float* lam, const float*
   BJX_CHECK_ARG(N >= 0, "bjx_smc_temper_value: bad sizes");
   if (N == 0) return 0;
   BJX_CHECK_ARG(lam && logprior && loglik && logp_out, "bjx_smc_temper_value: null pointer");
-  hipLaunchKernelGGL(k_temper_value, dim3(flat_grid(N)), dim3(kBlock), 0, (hipStream_t)stream, N, lam, logprior,
-                     loglik, logp_out);
+  hipLaunchKernelGGL(k_temper_value, dim3(bjx_flat_grid(N, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, N, lam,
+                     logprior, loglik, logp_out);
   return bjx_check_launch("bjx_smc_temper_value");
 }
 

@@ -5,28 +5,26 @@
 //
 // Every iteration weighs the P = i * N particles of all earlier iterations, so unlike the one-workgroup reductions of
 // bjx_smc.hip these use the whole device.  A reduction is launch-separated, as the prefix scan is: one workgroup per
-// tile of kPsTile particles writes the tile's (max, S1, S2) in fp64, S_k = sum exp(k (lw - max)) against the tile's
+// tile of kSmcTile particles writes the tile's (max, S1, S2) in fp64, S_k = sum exp(k (lw - max)) against the tile's
 // OWN maximum, and a later launch of one workgroup rescales and adds the tile triples.  The tiling is fixed by P alone
 // (never by the grid) and every sum has a fixed tree, so results are reproducible bit for bit; no workgroup waits on
 // another.  An evaluation of the bisection's f is one such pair of launches; the bracket lives in the workspace, so
-// the number of launches does not depend on the data and nothing is read back by the host.
+// the number of launches does not depend on the data and nothing is read back by the host.  Which log-weights count,
+// the order of a workgroup's sums and the tile size are bjx_smc_dev.h's, shared with bjx_smc.hip.
 #include <math.h>
 
 #include "../../include/bjx_hip.h"
 #include "bjx_device.h"
 #include "bjx_host.h"
 #include "bjx_rows.h"
+#include "bjx_smc_dev.h"
 
 using namespace bjx;
 
 namespace {
 
-constexpr int kPsItems = 4;                     // consecutive particles per thread
-constexpr int kPsTile = kBlock * kPsItems;      // 1024 particles per workgroup
 constexpr int kCombBlock = 1024;                // the one workgroup that adds the tile triples
 constexpr int kCombWaves = kCombBlock / BJX_WAVE;
-constexpr int64_t kMaxParticles = (int64_t)1 << 24;  // resampling positions are formed in fp32
-constexpr int kHalvings = 30;
 constexpr double kNegInf = -__builtin_inf();
 
 // Head of the workspace; the tile triples follow it.
@@ -39,38 +37,11 @@ struct PsHead {
 constexpr int64_t kHeadBytes = 64;
 static_assert(sizeof(PsHead) <= kHeadBytes, "workspace head");
 
-// tempered.py::log_weights_fn's rule (log_weight() of bjx_smc.hip): lam == 0 gives 0 whatever ll is.
-__device__ __forceinline__ float ps_product(float lam, float ll) { return lam == 0.0f ? 0.0f : lam * ll; }
-// A NaN or -inf log-weight is a particle of weight 0 and takes no part in any sum (+inf counts, as in bjx_smc.hip).
-__device__ __forceinline__ bool ps_counts(double lw) { return lw == lw && lw != kNegInf; }
 // lw_j = (double)(fp32 lam * ll_j) - (double) den_j: both terms are fp32 values, so the difference is exact in fp64.
+// The product, and which lw_j count, follow the weighting rule of bjx_smc_dev.h.  A term of the mixture denominator
+// has the same form, with log_Z_s in the place of den_j.
 __device__ __forceinline__ double ps_log_weight(float lam, float ll, float den) {
-  return (double)ps_product(lam, ll) - (double)den;
-}
-
-template <int WAVES>
-__device__ __forceinline__ double ps_block_sum(double v, double* sh) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int k = 0; k < WAVES; ++k) t += sh[k];
-  __syncthreads();
-  return t;
-}
-
-template <int WAVES>
-__device__ __forceinline__ double ps_block_max(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = sh[0];
-#pragma unroll
-  for (int k = 1; k < WAVES; ++k) t = fmax(t, sh[k]);
-  __syncthreads();
-  return t;
+  return (double)tempered_product(lam, ll) - (double)den;
 }
 
 // persistent_sampling.py::compute_log_persistent_weights, the mixture denominator:
@@ -85,9 +56,9 @@ k_ps_denominator(int64_t P, int64_t n_terms, const float* __restrict__ ll_p, con
     const float ll = ll_p[j];
     double m = kNegInf;
     for (int64_t s = 0; s < n_terms; ++s)
-      m = fmax(m, (double)ps_product(schedule[s], ll) - (double)log_Z[s]);  // (fmax drops a NaN; the sum keeps it)
+      m = fmax(m, ps_log_weight(schedule[s], ll, log_Z[s]));  // (fmax drops a NaN; the sum keeps it)
     double sum = 0.0;
-    for (int64_t s = 0; s < n_terms; ++s) sum += exp(((double)ps_product(schedule[s], ll) - (double)log_Z[s]) - m);
+    for (int64_t s = 0; s < n_terms; ++s) sum += exp(ps_log_weight(schedule[s], ll, log_Z[s]) - m);
     den_out[j] = (float)(m + log(sum) - log_terms);
   }
 }
@@ -109,25 +80,25 @@ k_ps_tile_partials(int64_t P, const float* __restrict__ ll, const float* __restr
     if (head->done) return;
     lam = head->lam;
   }
-  const int64_t j0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kPsItems;
-  double lw[kPsItems];
+  const int64_t j0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kSmcItems;
+  double lw[kSmcItems];
   double m = kNegInf;
 #pragma unroll
-  for (int e = 0; e < kPsItems; ++e) {
+  for (int e = 0; e < kSmcItems; ++e) {
     lw[e] = (j0 + e < P) ? ps_log_weight(lam, ll[j0 + e], den[j0 + e]) : kNegInf;
-    if (ps_counts(lw[e])) m = fmax(m, lw[e]);
+    if (lw_counts(lw[e])) m = fmax(m, lw[e]);
   }
-  m = ps_block_max<kWavesPerBlock>(m, sh);
+  m = block_max<kWavesPerBlock>(m, sh);
   double s1 = 0.0, s2 = 0.0;
 #pragma unroll
-  for (int e = 0; e < kPsItems; ++e)
-    if (ps_counts(lw[e])) {
+  for (int e = 0; e < kSmcItems; ++e)
+    if (lw_counts(lw[e])) {
       const double x = exp(lw[e] - m);  // m = +inf: NaN, as a log-sum-exp over a +inf term is
       s1 += x;
       s2 += x * x;
     }
-  s1 = ps_block_sum<kWavesPerBlock>(s1, sh);
-  s2 = ps_block_sum<kWavesPerBlock>(s2, sh);
+  s1 = block_sum<kWavesPerBlock>(s1, sh);
+  s2 = block_sum<kWavesPerBlock>(s2, sh);
   if (threadIdx.x == 0) {
     double* out = partials + 3 * (int64_t)blockIdx.x;
     out[0] = m;
@@ -142,7 +113,7 @@ __device__ __forceinline__ void ps_combine(int64_t n_tiles, const double* __rest
                                            double* S1, double* S2) {
   double m = kNegInf;
   for (int64_t b = threadIdx.x; b < n_tiles; b += kCombBlock) m = fmax(m, partials[3 * b]);
-  m = ps_block_max<kCombWaves>(m, sh);
+  m = block_max<kCombWaves>(m, sh);
   double s1 = 0.0, s2 = 0.0;
   for (int64_t b = threadIdx.x; b < n_tiles; b += kCombBlock) {
     const double mb = partials[3 * b];
@@ -153,8 +124,8 @@ __device__ __forceinline__ void ps_combine(int64_t n_tiles, const double* __rest
     }
   }
   *M = m;
-  *S1 = ps_block_sum<kCombWaves>(s1, sh);
-  *S2 = ps_block_sum<kCombWaves>(s2, sh);
+  *S1 = block_sum<kCombWaves>(s1, sh);
+  *S2 = block_sum<kCombWaves>(s2, sh);
 }
 
 // persistent_sampling.py::compute_log_Z: lse = logsumexp(lw), log_Z = lse - log P; -inf when no particle counts.
@@ -182,7 +153,7 @@ k_ps_write_weights(int64_t P, const float* __restrict__ ll, const float* __restr
   const bool none = lse == kNegInf;
   for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < P; j += (int64_t)gridDim.x * kBlock) {
     const double lw = ps_log_weight(lam, ll[j], den[j]);
-    const bool ok = ps_counts(lw);
+    const bool ok = lw_counts(lw);
     if (lw_out) lw_out[j] = none ? __builtin_nanf("") : (ok ? (float)(lw - lse) : -__builtin_inff());
     if (w_out) w_out[j] = none ? __builtin_nanf("") : (ok ? (float)exp(lw - lse) : 0.0f);
   }
@@ -233,18 +204,13 @@ k_ps_bracket(int64_t n_tiles, int it, double log_target, const float* __restrict
   head->lam = lam_old + 0.5f * (lo + hi);
 }
 
-int64_t ps_tiles(int64_t P) { return (P + kPsTile - 1) / kPsTile; }
-
-unsigned ps_flat_grid(int64_t n_items) {
-  const int64_t b = (n_items + kBlock - 1) / kBlock;
-  return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
+int64_t ps_tiles(int64_t P) { return (P + kSmcTile - 1) / kSmcTile; }
 
 }  // namespace
 
 extern "C" {
 
-int bjx_smc_persistent_tile(void) { return kPsTile; }
+int bjx_smc_persistent_tile(void) { return kSmcTile; }
 
 int64_t bjx_smc_persistent_workspace_bytes(int64_t P) {
   if (P < 1 || P > kMaxParticles) return 0;
@@ -257,7 +223,7 @@ int bjx_smc_persistent_denominator(void* stream, int64_t P, int64_t n_terms, con
                 "bjx_smc_persistent_denominator: bad sizes");
   if (P == 0) return 0;
   BJX_CHECK_ARG(loglik && schedule && log_Z && den_out, "bjx_smc_persistent_denominator: null pointer");
-  hipLaunchKernelGGL(k_ps_denominator, dim3(ps_flat_grid(P)), dim3(kBlock), 0, (hipStream_t)stream, P, n_terms,
+  hipLaunchKernelGGL(k_ps_denominator, dim3(bjx_flat_grid(P, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, P, n_terms,
                      loglik, schedule, log_Z, den_out);
   return bjx_check_launch("bjx_smc_persistent_denominator");
 }
@@ -275,7 +241,7 @@ int bjx_smc_persistent_weights(void* stream, int64_t P, const float* loglik, con
                      (const float*)nullptr, 0, (const PsHead*)head, partials);
   hipLaunchKernelGGL(k_ps_lse, dim3(1), dim3(kCombBlock), 0, s, P, nt, (const double*)partials, head, log_Z_out);
   if (log_weights_out || weights_out)
-    hipLaunchKernelGGL(k_ps_write_weights, dim3(ps_flat_grid(P)), dim3(kBlock), 0, s, P, loglik, den, lam,
+    hipLaunchKernelGGL(k_ps_write_weights, dim3(bjx_flat_grid(P, kBlock)), dim3(kBlock), 0, s, P, loglik, den, lam,
                        (const PsHead*)head, log_weights_out, weights_out);
   return bjx_check_launch("bjx_smc_persistent_weights");
 }

@@ -21,7 +21,7 @@ tempered step's: ``den = 0``, ``lw = lam * ll``, ``logZ_1 = log mean exp``.
 
 Deliberate differences from the reference:
 
-* ``lambda_s * ll`` is exactly 0 when ``lambda_s == 0`` whatever ``ll`` is (the rule of ``bjx_smc_reweight``), and a
+* ``lambda_s * ll`` is exactly 0 when ``lambda_s == 0`` whatever ``ll`` is (the weighting rule of ``csrc/bjx_smc_dev.h``), and a
   NaN or ``-inf`` log-weight is a particle of weight 0 that takes no part in any sum.  If no particle counts the
   weights are NaN and ``logZ_i = -inf``; no host check is made for it.
 * ``iteration`` is a Python int (the step count is known on the host), so nothing is read back from the device.

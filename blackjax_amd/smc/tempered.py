@@ -16,9 +16,10 @@ No temperature is baked into a traced or recorded function and no new closure re
 The temperature, the increment and the weights stay on the device: the only host reads are the caller's own
 (``while state.lmbda < 1`` reads 4 bytes).
 
-A particle whose log-likelihood is ``-inf`` or NaN gets weight 0.  If EVERY particle is like that (and the
-temperature moved) the weights are NaN and the increment is ``-inf``; no host check is made for it.  With
-``lam_new == lam_old`` the weights are uniform whatever the log-likelihoods are.
+A particle whose log-likelihood is ``-inf`` or NaN gets weight 0 (the weighting rule of
+``csrc/bjx_smc_dev.h``).  If EVERY particle is like that (and the temperature moved) the weights are NaN and the
+increment is ``-inf``; no host check is made for it.  With ``lam_new == lam_old`` the weights are uniform whatever the
+log-likelihoods are.
 
 ``update_strategy`` decides how the resampled particles are moved and how many are resampled: ``update_and_take_last``
 (all ``N``, the last of ``num_mcmc_steps`` states kept) or ``blackjax_amd.smc.waste_free.waste_free_smc(N, p)``

@@ -162,6 +162,29 @@ def test_non_finite_loglikelihoods(dev, n):
     np.testing.assert_allclose(t2n(inc_g), inc_r, rtol=RTOL, atol=ATOL)
 
 
+@pytest.mark.parametrize("n", [65, T + 1])
+def test_log_ess_drops_non_finite_log_weights(dev, n):
+    """``-inf`` and NaN log-weights are particles of weight 0: ``log_ess`` is that of the entries that count."""
+    lw = rsmc.log_weights(f32(0.4), _loglik_values(n))
+    lw[[3, 17, n - 1]] = -np.inf
+    lw[[5, 40]] = np.nan
+    expected = rsmc.log_ess(lw)
+    print("n", n, "log_ess", expected)
+    assert np.isfinite(expected) and expected == rsmc.log_ess(lw[np.isfinite(lw)])
+    np.testing.assert_allclose(t2n(smc.ess.log_ess(dev_t(lw, dev))), expected, rtol=RTOL, atol=ATOL)
+
+
+@pytest.mark.parametrize("n", [65, T + 1])
+def test_reweight_with_no_particle_of_positive_weight(dev, n):
+    """Every log-likelihood ``-inf`` and the temperature moves: every weight NaN, the increment exactly ``-inf``."""
+    ll = np.full(n, -np.inf, f32)
+    w_g, inc_g, lam_out = smc.base.reweight(dev_t(ll, dev), dev_t(f32(0.25), dev), dev_t(f32(0.5), dev))
+    w_r, inc_r = rsmc.reweight(ll, f32(0.25), f32(0.5))
+    assert np.all(np.isnan(w_r)) and inc_r == -np.inf
+    assert w_g.shape == (n,) and np.all(np.isnan(t2n(w_g)))
+    assert f32(inc_g.item()) == inc_r and f32(lam_out.item()) == f32(0.5)
+
+
 # ----------------------------------------------------------------------------- full steps
 def _step_case(d):
     """Zero-mean diagonal Gaussians as prior and likelihood (bjx.targets.DiagGaussian / oracle diag_gaussian evaluate
