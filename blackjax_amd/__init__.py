@@ -110,6 +110,9 @@ adaptive_persistent_sampling_smc = GenerateSamplingAPI(smc.adaptive_persistent_s
 # re-estimated after every temperature (smc.tuning: column moments of the particles are a HIP kernel)
 inner_kernel_tuning = GenerateSamplingAPI(smc.inner_kernel_tuning.as_top_level_api, smc.inner_kernel_tuning.init,
                                           smc.inner_kernel_tuning.build_kernel)
+# Pretuning (blackjax/smc/pretuning.py): tempered / adaptive tempered SMC with one parameter value per particle; before
+# every step the values are scored by the ESJD of a trial transition, jittered and resampled (three HIP kernels)
+pretuning = GenerateSamplingAPI(smc.pretuning.as_top_level_api, smc.pretuning.init, smc.pretuning.build_kernel)
 # Stochastic-gradient MCMC (blackjax/sgmcmc/sgld.py, sghmc.py, sgnht.py, csgld.py): the gradient is a minibatch estimate
 # from the user's callable, the noise draw + diffusion update (+ thermostat) is one fused launch per step; csgld adds
 # one launch for its per-chain energy histogram
@@ -118,4 +121,4 @@ sghmc = GenerateSamplingAPI(sgmcmc.sghmc.as_top_level_api, sgmcmc.sghmc.init, sg
 sgnht = GenerateSamplingAPI(sgmcmc.sgnht.as_top_level_api, sgmcmc.sgnht.init, sgmcmc.sgnht.build_kernel)
 csgld = GenerateSamplingAPI(sgmcmc.csgld.as_top_level_api, sgmcmc.csgld.init, sgmcmc.csgld.build_kernel)
 
-__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "orbital_hmc", "periodic_orbital", "barker", "barker_proposal", "elliptical_slice", "mgrad_gaussian", "marginal_latent_gaussian", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "persistent_sampling_smc", "adaptive_persistent_sampling_smc", "inner_kernel_tuning", "smc", "sgld", "sghmc", "sgnht", "csgld", "sgmcmc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]
+__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "orbital_hmc", "periodic_orbital", "barker", "barker_proposal", "elliptical_slice", "mgrad_gaussian", "marginal_latent_gaussian", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "persistent_sampling_smc", "adaptive_persistent_sampling_smc", "inner_kernel_tuning", "pretuning", "smc", "sgld", "sghmc", "sgnht", "csgld", "sgmcmc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]

@@ -317,6 +317,11 @@ SIGNATURES.update({
     "bjx_smc_scatter_rows": [c_void_p, c_int64, c_int64, _f32p, c_int64, c_int64, _f32p],
     "bjx_smc_moments_tile": [],
     "bjx_smc_particle_moments": [c_void_p, c_int64, c_int64, _f32p, c_void_p, _f32p, _f32p],
+    # pretuning: ESJD per particle, alpha + measure normalised, jittered parameter rows gathered by ancestor
+    "bjx_smc_esjd": [c_void_p, c_int64, c_int64, _f32p, _f32p, _f32p, _f32p, c_int64, _f32p],
+    "bjx_smc_pretune_weights": [c_void_p, c_int64, c_float, _f32p, _f32p],
+    "bjx_smc_jitter_gather": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, c_int64, _f32p, c_void_p, _f32p, c_int64,
+                              ctypes.c_int32, _f32p],
     # persistent sampling (bjx_smc_persistent_tile returns the reduction's tile size, not a status)
     "bjx_smc_persistent_tile": [],
     "bjx_smc_persistent_denominator": [c_void_p, c_int64, c_int64, _f32p, _f32p, _f32p, _f32p],

@@ -16,7 +16,8 @@ log-density and trace both user callables once per temperature, so the inner ker
 ``root_solver`` and ``update_strategy`` through to it.  The override is a dict of keyword arguments of the move, as
 ``mcmc_parameters`` is everywhere in ``blackjax_amd.smc``; nothing in a step is read back by the host.
 
-Out of scope: partial posteriors and pretuning.
+Out of scope: partial posteriors.  Parameters kept per particle and adapted BEFORE a step are
+``blackjax_amd.smc.pretuning``.
 """
 from __future__ import annotations
 
@@ -42,14 +43,15 @@ def init(alg_init_fn: Callable, position, initial_parameter_value) -> StateWithP
     return StateWithParameterOverride(alg_init_fn(position), initial_parameter_value)
 
 
-def _inner_build_kernel(smc_algorithm) -> tuple[Callable, bool]:
-    """-> (the ``build_kernel`` of the algorithm, whether it is the adaptive one)."""
+def _inner_build_kernel(smc_algorithm, wrapper: str = "inner_kernel_tuning") -> tuple[Callable, bool]:
+    """-> (the ``build_kernel`` of the algorithm, whether it is the adaptive one); ``wrapper`` names the caller in the
+    error (``smc.pretuning`` resolves its inner algorithm here too)."""
     build = getattr(smc_algorithm, "build_kernel", None)
     if build is tempered.build_kernel:
         return build, False
     if build is adaptive_tempered.build_kernel:
         return build, True
-    raise TypeError("inner_kernel_tuning wraps blackjax_amd.tempered_smc or blackjax_amd.adaptive_tempered_smc, got "
+    raise TypeError(f"{wrapper} wraps blackjax_amd.tempered_smc or blackjax_amd.adaptive_tempered_smc, got "
                     f"{smc_algorithm!r}")
 
 

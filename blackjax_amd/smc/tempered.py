@@ -24,11 +24,11 @@ log-likelihoods are.
 ``update_strategy`` decides how the resampled particles are moved and how many are resampled: ``update_and_take_last``
 (all ``N``, the last of ``num_mcmc_steps`` states kept) or ``blackjax_amd.smc.waste_free.waste_free_smc(N, p)``
 (``N / p`` ancestors, every state kept; ``SMCInfo.ancestors`` is then ``(N / p,)``).  The parameters of the move can
-be re-estimated between temperatures with ``blackjax_amd.smc.inner_kernel_tuning``.
+be re-estimated between temperatures with ``blackjax_amd.smc.inner_kernel_tuning``, or carried as one value per
+particle and adapted before every step with ``blackjax_amd.smc.pretuning``.
 
-Out of scope: partial-posteriors and pretuning (persistent sampling is ``blackjax_amd.smc.persistent_sampling``),
-pytrees of particles, and sharding the particles across GPUs (resampling is global: there is no ``chain_offset``
-here).
+Out of scope: partial-posteriors (persistent sampling is ``blackjax_amd.smc.persistent_sampling``), pytrees of
+particles, and sharding the particles across GPUs (resampling is global: there is no ``chain_offset`` here).
 """
 from __future__ import annotations
 

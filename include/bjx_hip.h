@@ -803,6 +803,32 @@ int64_t bjx_smc_particle_moments_workspace_bytes(int64_t N, int64_t D);
 int bjx_smc_particle_moments(void* stream, int64_t N, int64_t D, const float* x, void* workspace, float* mean_out,
                              float* std_out);
 
+/* Pretuning (blackjax.pretuning): a population of move parameters, one row per particle, scored by the expected
+ * squared jump distance of one trial transition, jittered and resampled by that score before every SMC step.  The
+ * ancestors are bjx_smc_resample_sorted's (BJX_SMC_MULTINOMIAL) from the weights below.  All three launch on the
+ * caller's stream and read nothing back.  1 <= N, M <= 2^24 ; 1 <= D, K <= 2^20.
+ *
+ * bjx_smc_esjd:  d_j = prev[i, j] - next[i, j] (fp32) ; s_i = sum_j d_j^2 / imm_j in fp64 (imm null: all ones;
+ *   otherwise imm[i * imm_stride + j], imm_stride 0 shared or D per particle) ;
+ *   measure_out[i] = (float)(s_i * (double) acc[i]), rounded once.  A measure that is NaN, +-inf or negative is stored
+ *   as exactly 0: a divergent or NaN trial then weighs alpha below and does not poison the sum.  One wavefront per
+ *   row; 16-byte accesses when D % 4 == 0 and the arrays are 16-byte aligned.
+ * bjx_smc_pretune_weights:  t_i = (double) alpha + (double) measure[i] ; S = sum t ; weights_out[i] = (float)(t_i / S),
+ *   uniform 1 / N when S == 0 (alpha 0 and nothing moved).  alpha >= 0 and finite.  One workgroup.
+ * bjx_smc_jitter_gather:  out[i, k] = jitter(P[a_i, k], sigma_k, z[a_i, k]), P (N, K), out (M, K), out of place,
+ *   a_i = ancestors[i] clamped into [0, N), z = normal(key, (N, K)) (element a_i * K + k: the noise belongs to the
+ *   SOURCE row, the reference adds it before it resamples), sigma_k = sigma[k * sigma_stride] (sigma_stride 0: one
+ *   scalar, 1: one value per column).  log_space 0: fmaf(sigma, z, p) ; log_space 1: p * exp(sigma * z), the product
+ *   and the exponential each rounded to fp32 -- for parameters that must stay positive.  One wavefront per output row,
+ *   one thread per row when K == 1.
+ * Replaces: smc/pretuning.py::esjd, update_parameter_distribution. */
+int bjx_smc_esjd(void* stream, int64_t N, int64_t D, const float* prev, const float* next, const float* acc,
+                 const float* imm, int64_t imm_stride, float* measure_out);
+int bjx_smc_pretune_weights(void* stream, int64_t N, float alpha, const float* measure, float* weights_out);
+int bjx_smc_jitter_gather(void* stream, uint32_t key0, uint32_t key1, int64_t N, int64_t M, int64_t K, const float* P,
+                          const int32_t* ancestors, const float* sigma, int64_t sigma_stride, int32_t log_space,
+                          float* out);
+
 /* Persistent sampling (blackjax.persistent_sampling_smc / adaptive_persistent_sampling_smc).  Iteration i weighs
  * the P = i * N particles of ALL earlier iterations against the mixture of their tempered targets:
  *   den_j = logsumexp_{s < n_terms}(a_sj - log_Z[s]) - log(n_terms), a_sj = schedule[s] * loglik[j] in fp32 (exactly 0
