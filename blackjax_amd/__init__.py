@@ -19,11 +19,11 @@ from . import mala as _mala
 from . import marginal_latent_gaussian
 from . import nuts as _nuts
 from . import periodic_orbital
-from . import adaptation, chees, diagnostics, distributed, integrators, meads, metrics, optim, random, random_walk, rtc, sgmcmc, smc, targets, util
+from . import adaptation, chees, diagnostics, distributed, integrators, meads, metrics, optim, random, random_walk, rtc, sgmcmc, smc, targets, util, vi
 from .adaptation import staged_adaptation, window_adaptation
 from .chees import chees_adaptation
 from .meads import meads_adaptation
-from .base import AdaptationAlgorithm, SamplingAlgorithm
+from .base import AdaptationAlgorithm, SamplingAlgorithm, VIAlgorithm
 from ._util import capturable, no_trace, returns_pair
 
 __version__ = "0.1.0"
@@ -38,6 +38,19 @@ class GenerateSamplingAPI:
         self.build_kernel = build_kernel
 
     def __call__(self, *args, **kwargs) -> SamplingAlgorithm:
+        return self.differentiable(*args, **kwargs)
+
+
+class GenerateVariationalAPI:
+    """blackjax/__init__.py ``GenerateVariationalAPI``: callable that also exposes ``init`` / ``step`` / ``sample``."""
+
+    def __init__(self, differentiable, init, step, sample):
+        self.differentiable = differentiable
+        self.init = init
+        self.step = step
+        self.sample = sample
+
+    def __call__(self, *args, **kwargs) -> VIAlgorithm:
         return self.differentiable(*args, **kwargs)
 
 
@@ -120,5 +133,9 @@ sgld = GenerateSamplingAPI(sgmcmc.sgld.as_top_level_api, sgmcmc.sgld.init, sgmcm
 sghmc = GenerateSamplingAPI(sgmcmc.sghmc.as_top_level_api, sgmcmc.sghmc.init, sgmcmc.sghmc.build_kernel)
 sgnht = GenerateSamplingAPI(sgmcmc.sgnht.as_top_level_api, sgmcmc.sgnht.init, sgmcmc.sgnht.build_kernel)
 csgld = GenerateSamplingAPI(sgmcmc.csgld.as_top_level_api, sgmcmc.csgld.init, sgmcmc.csgld.build_kernel)
+# Mean-field variational inference (blackjax/vi/meanfield_vi.py): a diagonal Gaussian fitted by stochastic gradient steps
+# on the KL estimate; the draw, the reduction of the (S, D) gradients and the optimiser updates are HIP kernels
+meanfield_vi = GenerateVariationalAPI(vi.meanfield_vi.as_top_level_api, vi.meanfield_vi.init, vi.meanfield_vi.step,
+                                      vi.meanfield_vi.sample)
 
-__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "orbital_hmc", "periodic_orbital", "barker", "barker_proposal", "elliptical_slice", "mgrad_gaussian", "marginal_latent_gaussian", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "persistent_sampling_smc", "adaptive_persistent_sampling_smc", "inner_kernel_tuning", "pretuning", "smc", "sgld", "sghmc", "sgnht", "csgld", "sgmcmc", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "capturable", "returns_pair", "no_trace"]
+__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "orbital_hmc", "periodic_orbital", "barker", "barker_proposal", "elliptical_slice", "mgrad_gaussian", "marginal_latent_gaussian", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "persistent_sampling_smc", "adaptive_persistent_sampling_smc", "inner_kernel_tuning", "pretuning", "smc", "sgld", "sghmc", "sgnht", "csgld", "sgmcmc", "meanfield_vi", "vi", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "VIAlgorithm", "capturable", "returns_pair", "no_trace"]

@@ -29,6 +29,15 @@ class SamplingAlgorithm(tuple):
         return f"SamplingAlgorithm(init={self[0]!r}, step={self[1]!r})"
 
 
+class VIAlgorithm(NamedTuple):
+    """``init(position) -> State`` ; ``step(rng_key, state) -> (State, Info)`` ;
+    ``sample(rng_key, state, num_samples=1) -> (num_samples, dim)`` (blackjax/base.py ``VIAlgorithm``)."""
+
+    init: Callable
+    step: Callable
+    sample: Callable
+
+
 class AdaptationAlgorithm(NamedTuple):
     """``run(rng_key, position, num_steps=1000) -> (AdaptationResults, info)``
     (blackjax/base.py:148-151)."""

@@ -377,20 +377,6 @@ k_scatter_rows(int64_t M, int64_t D, const float* __restrict__ x, int64_t row0, 
 // ---- column moments of the particles -----------------------------------------------------------------------
 constexpr int kMomTile = 256;  // rows per workgroup: fixed, so the partials depend on (N, D) alone
 
-// columns per workgroup: at most 64 (one wavefront across a row piece of 256 bytes), so that wide particles spread
-// over D / 64 workgroups per tile and every column still has 4 row groups
-__host__ __device__ inline int mom_cols(int64_t D) { return D >= 64 ? 64 : (D >= 16 ? 16 : 4); }
-
-// Adds the kBlock / cw row groups of a column in a fixed order; every thread of the column gets the total.
-__device__ __forceinline__ double column_total(double v, double* sh, int cw) {
-  sh[threadIdx.x] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int k = threadIdx.x % cw; k < kBlock; k += cw) t += sh[k];
-  __syncthreads();
-  return t;
-}
-
 // Workgroup (tile, column block): cw consecutive columns (consecutive threads: reads coalesced along D) by
 // kBlock / cw row groups.  part[(tile * D + j) * 2 + {0, 1}] = the tile's mean of column j and its sum of squared
 // deviations from that mean, fp64.
@@ -554,7 +540,7 @@ int bjx_smc_particle_moments(void* stream, int64_t N, int64_t D, const float* x,
                 "bjx_smc_particle_moments: bad sizes");
   BJX_CHECK_ARG(x && workspace && mean_out, "bjx_smc_particle_moments: null pointer");
   const int64_t tiles = mom_tiles(N);
-  const int cw = mom_cols(D);
+  const int cw = column_block(D);
   double* part = (double*)workspace;
   hipLaunchKernelGGL(k_moments_tile, dim3((unsigned)tiles, (unsigned)((D + cw - 1) / cw)), dim3(kBlock), 0,
                      (hipStream_t)stream, N, D, cw, x, part);

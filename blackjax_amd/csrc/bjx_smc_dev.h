@@ -1,5 +1,6 @@
 // Device helpers shared by the SMC kernels (gfx950): the weighting rule, the workgroup reductions and the sizes that
-// bjx_smc.hip and bjx_smc_persistent.hip must agree on.  Device code only, included by those two files only.
+// bjx_smc.hip and bjx_smc_persistent.hip must agree on.  Device code only, included by the SMC files and, for the
+// workgroup and column reductions, by bjx_vi.hip.
 #pragma once
 
 #include "bjx_rows.h"
@@ -29,6 +30,23 @@ __device__ __forceinline__ double block_sum(double v, double* sh) {
   double t = 0.0;
 #pragma unroll
   for (int k = 0; k < WAVES; ++k) t += sh[k];
+  __syncthreads();
+  return t;
+}
+
+// Column reductions of an (N, D) array (the particle moments; the gradient batch of bjx_vi.hip).  A workgroup of
+// kBlock threads is cw consecutive columns (consecutive threads: reads coalesced along D) by kBlock / cw row groups.
+// cw is at most 64 (one wavefront across a row piece of 256 bytes), so that wide rows spread over D / 64 workgroups per
+// row tile and every column still has 4 row groups.
+__host__ __device__ inline int column_block(int64_t D) { return D >= 64 ? 64 : (D >= 16 ? 16 : 4); }
+
+// Adds the kBlock / cw row groups of a column in a fixed order; every thread of the column gets the total.  sh: kBlock
+// slots, free again on return.
+__device__ __forceinline__ double column_total(double v, double* sh, int cw) {
+  sh[threadIdx.x] = v;
+  __syncthreads();
+  double t = 0.0;
+  for (int k = threadIdx.x % cw; k < kBlock; k += cw) t += sh[k];
   __syncthreads();
   return t;
 }

@@ -860,6 +860,50 @@ int bjx_smc_persistent_weights(void* stream, int64_t P, const float* loglik, con
 int bjx_smc_persistent_ess_solve(void* stream, int64_t P, const float* loglik, const float* den, float target,
                                  const float* lam_old, void* workspace, float* delta_out, float* lam_new_out);
 
+/* ---- VI --------------------------------------------------------------------------------------------------------
+ * Mean-field variational inference (blackjax.meanfield_vi): a diagonal Gaussian q = N(mu, exp(rho)^2) fitted by
+ * stochastic gradient steps on KL(q || p).  The S Monte-Carlo draws of a step are an (S, D) row batch; eps below is
+ * normal(key, (S, D)), element (s, d) at flat index s * D + d of the key itself, and sigma_d = exp_cr(rho[d]) (the
+ * exponential in fp64, rounded once to fp32).  Every launch is on the caller's stream and reads nothing back.
+ * 1 <= S <= 2^24 ; 1 <= D <= 2^20 ; S * D <= 2^31.
+ *
+ * bjx_vi_meanfield_sample:  z_out[s, d] = fmaf(sigma_d, eps_sd, mu[d]) -- ONE fused multiply-add.  A thread owns
+ *   16-byte pieces of the flat (S * D,) array when D % 4 == 0 and mu, rho and z_out are 16-byte aligned, 4-byte
+ *   elements otherwise (S may be 5 and D 2^20, so the mapping is flat rather than a wavefront per row).
+ * bjx_vi_meanfield_grad:  from G (S, D) and logp (S,), the value and gradient of the target at z, the gradients of
+ *   the KL estimate with respect to mu and rho and the estimate itself.  eps is regenerated from the key, so no
+ *   (S, D) noise array exists.  Every term is formed in fp64 from the fp32 G, eps and sigma (eps / sigma as eps times
+ *   the fp64 reciprocal of sigma), summed in fp64 in a fixed order and rounded once:
+ *     stl = 1 (sticking the landing):  g_mu[d] = mean_s(-eps_sd / sigma_d - G_sd)
+ *                                      g_rho[d] = mean_s(-eps_sd^2 - G_sd sigma_d eps_sd)
+ *     stl = 0:                         g_mu[d] = -mean_s G_sd ;  g_rho[d] = -1 - mean_s(G_sd sigma_d eps_sd)
+ *     *kl_out = -(sum_sd eps_sd^2) / (2 S) - sum_d rho[d] - D log(2 pi) / 2 - mean_s logp[s]
+ *   Three launches: one workgroup per tile of bjx_vi_meanfield_tile() rows and block of columns (consecutive threads
+ *   on consecutive columns) writes the tile's partial sums, one thread per column adds the tiles in order, one
+ *   workgroup forms the scalar.  Launch-separated, and the tiling depends on (S, D) alone: the result is reproducible
+ *   bit for bit.  A NaN in G[s, d] reaches g_mu[d] and g_rho[d] only.  workspace:
+ *   bjx_vi_meanfield_grad_workspace_bytes(S, D) bytes (0 for sizes out of range), 8-byte aligned, contents scratch.
+ * Replaces: vi/meanfield_vi.py::sample, step (the Monte-Carlo KL estimate and its jax.value_and_grad). */
+int bjx_vi_meanfield_tile(void);
+int bjx_vi_meanfield_sample(void* stream, uint32_t key0, uint32_t key1, int64_t S, int64_t D, const float* mu,
+                            const float* rho, float* z_out);
+int64_t bjx_vi_meanfield_grad_workspace_bytes(int64_t S, int64_t D);
+int bjx_vi_meanfield_grad(void* stream, uint32_t key0, uint32_t key1, int64_t S, int64_t D, int32_t stl,
+                          const float* G, const float* logp, const float* rho, void* workspace, float* g_mu_out,
+                          float* g_rho_out, float* kl_out);
+/* Element-wise optimiser updates over an (n,) tensor, out of place, mirroring blackjax_amd/optim.py operation by
+ * operation in fp32 with no contraction and IEEE division and square root:
+ *   adam:  m = (one_minus_b1 * g) + (b1 * mu) ;  v = (one_minus_b2 * (g * g)) + (b2 * nu) ;
+ *          u_out = neg_lr * ((m / c1) / (sqrtf(v / c2 + eps_root) + eps)) ;  mu_out = m ;  nu_out = v
+ *          c1 = 1 - b1^count and c2 = 1 - b2^count are formed on the host from the host's step count.
+ *   sgd:   u_out = neg_lr * g
+ * 0 <= n <= 2^31 ; n == 0 is a no-op.
+ * Replaces: optax.adam / optax.sgd applied to the (mu, rho) pytree of vi/meanfield_vi.py::step. */
+int bjx_optim_adam(void* stream, int64_t n, float b1, float b2, float one_minus_b1, float one_minus_b2, float c1,
+                   float c2, float eps, float eps_root, float neg_lr, const float* g, const float* mu, const float* nu,
+                   float* mu_out, float* nu_out, float* u_out);
+int bjx_optim_sgd(void* stream, int64_t n, float neg_lr, const float* g, float* u_out);
+
 /* Built-in synthetic targets (value + gradient in one pass, fp64-accumulated logp) used
  * as the "user callable" by the bench and parity tests.
  *   diag gaussian:  g = -(q*inv_var) ; logp = 0.5 * sum q*g     (tests/fixtures.py:60-78)
