@@ -137,5 +137,9 @@ csgld = GenerateSamplingAPI(sgmcmc.csgld.as_top_level_api, sgmcmc.csgld.init, sg
 # on the KL estimate; the draw, the reduction of the (S, D) gradients and the optimiser updates are HIP kernels
 meanfield_vi = GenerateVariationalAPI(vi.meanfield_vi.as_top_level_api, vi.meanfield_vi.init, vi.meanfield_vi.step,
                                       vi.meanfield_vi.sample)
+# Full-rank variational inference (blackjax/vi/fullrank_vi.py): a Gaussian with a Cholesky-factored covariance; the
+# triangular product of the draw, the batched triangular solve and the outer-product reduction are HIP kernels
+fullrank_vi = GenerateVariationalAPI(vi.fullrank_vi.as_top_level_api, vi.fullrank_vi.init, vi.fullrank_vi.step,
+                                     vi.fullrank_vi.sample)
 
-__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "orbital_hmc", "periodic_orbital", "barker", "barker_proposal", "elliptical_slice", "mgrad_gaussian", "marginal_latent_gaussian", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "persistent_sampling_smc", "adaptive_persistent_sampling_smc", "inner_kernel_tuning", "pretuning", "smc", "sgld", "sghmc", "sgnht", "csgld", "sgmcmc", "meanfield_vi", "vi", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "VIAlgorithm", "capturable", "returns_pair", "no_trace"]
+__all__ = ["hmc", "nuts", "mhmc", "hmc_family", "multinomial_hmc", "dynamic_hmc", "dhmc", "dmhmc", "ghmc", "mala", "orbital_hmc", "periodic_orbital", "barker", "barker_proposal", "elliptical_slice", "mgrad_gaussian", "marginal_latent_gaussian", "rmh", "irmh", "additive_step_random_walk", "normal_random_walk", "random_walk", "tempered_smc", "adaptive_tempered_smc", "persistent_sampling_smc", "adaptive_persistent_sampling_smc", "inner_kernel_tuning", "pretuning", "smc", "sgld", "sghmc", "sgnht", "csgld", "sgmcmc", "meanfield_vi", "fullrank_vi", "vi", "window_adaptation", "staged_adaptation", "chees_adaptation", "meads_adaptation", "chees", "meads", "optim", "adaptation", "diagnostics", "distributed", "util", "metrics", "integrators", "random", "rtc", "targets", "SamplingAlgorithm", "AdaptationAlgorithm", "VIAlgorithm", "capturable", "returns_pair", "no_trace"]

@@ -372,11 +372,17 @@ SIGNATURES.update({
     "bjx_vi_meanfield_sample": [c_void_p, c_uint32, c_uint32, c_int64, c_int64] + [_f32p] * 3,
     "bjx_vi_meanfield_grad": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, ctypes.c_int32] + [_f32p] * 3
                              + [c_void_p] + [_f32p] * 3,
+    "bjx_vi_fullrank_tile": [],
+    "bjx_vi_fullrank_block": [],
+    "bjx_vi_fullrank_sample": [c_void_p, c_uint32, c_uint32, c_int64, c_int64] + [_f32p] * 3,
+    "bjx_vi_fullrank_grad": [c_void_p, c_uint32, c_uint32, c_int64, c_int64, ctypes.c_int32] + [_f32p] * 3
+                            + [c_void_p] + [_f32p] * 3,
     "bjx_optim_adam": [c_void_p, c_int64] + [c_float] * 9 + [_f32p] * 6,
     "bjx_optim_sgd": [c_void_p, c_int64, c_float] + [_f32p] * 2,
 })
 INT64_FUNCTIONS = {"bjx_pool_workspace_bytes": [c_int64, c_int64],
                    "bjx_vi_meanfield_grad_workspace_bytes": [c_int64, c_int64],
+                   "bjx_vi_fullrank_grad_workspace_bytes": [c_int64, c_int64],
                    "bjx_meads_workspace_bytes": [c_int64, c_int64],
                    "bjx_smc_resample_workspace_bytes": [c_int64],
                    "bjx_smc_resample_sorted_workspace_bytes": [c_int64, c_int64],

@@ -10,6 +10,10 @@
 // the flat index s * D + d the draw used, so no (S, D) noise array exists.  Nothing is read back, no workgroup waits on
 // another, and the tiling depends on (S, D) alone: results are reproducible bit for bit.  The piece loads, stores and
 // normal draws are bjx_rows.h's, the workgroup sums bjx_smc_dev.h's.
+//
+// Full-rank variational inference (blackjax/vi/fullrank_vi.py) follows below the mean-field kernels: the triangular
+// product of the draw, the blocked triangular solve of the sticking-the-landing term and the lower-triangular
+// outer-product reduction, with the same noise layout, column reduction and KL launch.
 #include <math.h>
 
 #include "../../include/bjx_hip.h"
@@ -174,6 +178,422 @@ bool vi_sizes_ok(int64_t S, int64_t D) {
 int64_t vi_tiles(int64_t S) { return (S + kViTile - 1) / kViTile; }
 int64_t vi_col_blocks(int64_t D) { return (D + kBlock - 1) / kBlock; }
 
+// ----------------------------------------------------------------------------------------------------------------
+// Full-rank VI: q = N(mu, L L^T), L lower triangular and packed in chol (include/bjx_hip.h "VI"): chol[i] = log L_ii,
+// L_ij = chol[D + i (i - 1) / 2 + j] for j < i, so a row of L is contiguous in j.  The triangle is cut into
+// kFrBlock x kFrBlock blocks and the draws into tiles of kFrTile rows.  Every sum is an fp64 fma chain in a fixed
+// order over the fp32 inputs (a product of two fp32 values is exact in fp64), rounded once to fp32 at the end.
+constexpr int kFrTile = 64;    // draws per workgroup of the draw and the solve: bjx_vi_fullrank_tile
+constexpr int kFrBlock = 64;   // columns per block of the triangle: bjx_vi_fullrank_block
+constexpr int kFrSub = 16;     // the solve's register sub-block inside a diagonal block
+constexpr int kFrOuterRows = 32;  // draws per LDS fill of the outer product
+constexpr int64_t kFrMaxDraws = (int64_t)1 << 20;
+constexpr int64_t kFrMaxCols = 4096;
+constexpr int64_t kFrMaxElems = (int64_t)1 << 27;  // S * D: the fp64 W workspace is at most 1 GiB
+constexpr int64_t kFrOuterGroups = 1024;           // the outer product splits S until about this many workgroups
+constexpr int kFrMaxChunks = 64;
+static_assert(kBlock == 256 && kFrTile == 64 && kFrBlock == 64, "the 16 x 16 thread grid of 4 x 4 micro-tiles");
+
+__device__ __forceinline__ int64_t fr_row(int64_t D, int64_t i) { return D + i * (i - 1) / 2; }  // of L_i0 in chol
+__device__ __forceinline__ double fr_eps(Key key, int64_t s, int64_t D, int64_t j) {
+  return (double)normal_from_bits(key_bits32(key, (uint64_t)(s * D + j)));
+}
+
+// eps[s + STRIDE e, j], e < 4, for the rows below `rows`: the four draws are independent straight-line code
+// (normal4_from_bits), where one wavefront per SIMD would otherwise wait out four dependent chains in turn.  A row at
+// or past `rows` gives 0; s >= rows gives no work at all.
+template <int STRIDE>
+__device__ __forceinline__ void fr_eps4(Key key, int64_t s, int64_t rows, int64_t D, int64_t j, float (&z)[4]) {
+  z[0] = z[1] = z[2] = z[3] = 0.0f;
+  if (s >= rows) return;
+  uint32_t bits[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int64_t r = s + STRIDE * e < rows ? s + STRIDE * e : s;
+    bits[e] = key_bits32(key, (uint64_t)(r * D + j));
+  }
+  float v[4];
+  normal4_from_bits(bits, v);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) z[e] = s + STRIDE * e < rows ? v[e] : 0.0f;
+}
+
+// z[s, i] = fp32(mu_i + sum_{j <= i} L_ij eps_sj), j ascending.  Workgroup (tile of kFrTile draws, block I of
+// kFrBlock columns) walks the column chunks 0 .. I of eps (those wholly above the diagonal are skipped), regenerates a
+// chunk into LDS once and reads the rows of L contiguously.  Thread (tx, ty) owns draws ty + 16 a and columns
+// tx + 16 b, a, b < 4; a tile with fewer than 64 draws skips the a it does not have.
+__global__ void __launch_bounds__(kBlock)
+k_fr_sample(Key key, int64_t S, int64_t D, const float* __restrict__ mu, const float* __restrict__ chol,
+            float* __restrict__ z) {
+  __shared__ float Ls[kFrBlock][kFrBlock + 1];
+  __shared__ float eS[kFrTile][kFrBlock + 1];
+  const int tid = threadIdx.x, tx = tid % 16, ty = tid / 16, lane = tid % 64, wv = tid / 64;
+  const int64_t s0 = (int64_t)blockIdx.x * kFrTile;
+  const int I = blockIdx.y;
+  const int64_t i0 = (int64_t)I * kFrBlock;
+  const int ns = (int)(S - s0 < kFrTile ? S - s0 : kFrTile);
+  const int ra = (ns + 15) / 16;
+  double acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+  // the next chunk's entries of L are loaded (one load per entry, all in flight together) while this one is used
+  float lreg[kFrBlock / 4];
+  auto load_chunk = [&](int c) {
+    const int64_t j = (int64_t)c * kFrBlock + lane;
+#pragma unroll
+    for (int e = 0; e < kFrBlock / 4; ++e) {
+      const int64_t i = i0 + wv + 4 * e;
+      lreg[e] = (i < D && j <= i) ? chol[j < i ? fr_row(D, i) + j : i] : 0.0f;
+    }
+  };
+  load_chunk(0);
+  for (int c = 0; c <= I; ++c) {
+    const int64_t j = (int64_t)c * kFrBlock + lane;
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < kFrBlock / 4; ++e) Ls[wv + 4 * e][lane] = lreg[e];
+    // the diagonal (j == i, in the last chunk): one exponential per lane, by the thread that loaded row `lane`
+    if (c == I && wv == lane % 4 && i0 + lane < D) {
+      float d = 0.0f;
+#pragma unroll
+      for (int e = 0; e < kFrBlock / 4; ++e) d = lane == wv + 4 * e ? lreg[e] : d;
+      Ls[lane][lane] = exp_cr(d);
+    }
+    for (int e4 = 0; e4 < kFrTile / 16; ++e4) {
+      float ev[4];
+      fr_eps4<4>(key, s0 + wv + 16 * e4, j < D ? s0 + ns : 0, D, j, ev);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) eS[wv + 16 * e4 + 4 * e][lane] = ev[e];
+    }
+    __syncthreads();
+    if (c < I) load_chunk(c + 1);
+    for (int jj = 0; jj < kFrBlock; ++jj) {
+      double l[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) l[b] = (double)Ls[tx + 16 * b][jj];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        if (a < ra) {
+          const double ev = (double)eS[ty + 16 * a][jj];
+#pragma unroll
+          for (int b = 0; b < 4; ++b) acc[a][b] = fma(l[b], ev, acc[a][b]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int s = ty + 16 * a;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int64_t i = i0 + tx + 16 * b;
+      if (s < ns && i < D) z[(s0 + s) * D + i] = (float)((double)mu[i] + acc[a][b]);
+    }
+  }
+}
+
+// STL only: L^T u_s = eps_s, U in fp64 into W, by a right-looking blocked back-substitution from the last column
+// block to the first, one launch per column block: the launch-separated form of a loop that a single workgroup per
+// tile of draws ran 10 to 20 times slower.  The running right-hand side r lives in W (columns not yet
+// solved) and starts as eps, regenerated where it is first needed.  Launch t = nb - 1 .. 0, workgroup (tile of
+// kFrTile draws, block K <= t): r_K -= sum_i L_iK u_i over the rows i of block t + 1, i descending (the block the
+// launch before solved; nothing for t = nb - 1, which has one workgroup per tile); then K < t writes r_K back, and K = t
+// solves its diagonal block -- L's block with its diagonal replaced by the fp64 reciprocals of L_jj and r to LDS, one
+// wavefront (a lane per draw) in register sub-blocks of kFrSub columns, u_j = r_j (1 / L_jj), then r_i -= L_ji u_j
+// for i < j, j descending -- and writes u.  Thread (tx, ty) owns draws ty + 16 a and columns 4 tx + b of its block.
+__global__ void __launch_bounds__(kBlock)
+k_fr_solve_step(Key key, int64_t S, int64_t D, int t, const float* __restrict__ chol, double* W) {
+  __shared__ double Ls[kFrBlock][kFrBlock];  // [row of L][column of L]
+  __shared__ double rT[kFrBlock][kFrTile];   // [column][draw]: u of block t + 1, then r and u of block t
+  const int tid = threadIdx.x, tx = tid % 16, ty = tid / 16, lane = tid % 64, wv = tid / 64;
+  const int64_t s0 = (int64_t)blockIdx.x * kFrTile;
+  const int ns = (int)(S - s0 < kFrTile ? S - s0 : kFrTile);
+  const int ra = (ns + 15) / 16;
+  const int nb = (int)((D + kFrBlock - 1) / kFrBlock);
+  const bool upd = t + 1 < nb;
+  const bool fresh = t + 2 >= nb;  // no launch has written r yet: it is eps
+  const int K = upd ? (int)blockIdx.y : t;
+  const int64_t k0 = (int64_t)K * kFrBlock;
+  double acc[4][4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    const int64_t k = k0 + 4 * tx + b;
+    float ev[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (fresh) fr_eps4<16>(key, s0 + ty, k < D ? s0 + ns : 0, D, k, ev);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int s = ty + 16 * a;
+      acc[a][b] = (double)ev[a];
+      if (!fresh && s < ns && k < D) acc[a][b] = W[(s0 + s) * D + k];
+    }
+  }
+  if (upd) {
+    const int64_t j0 = (int64_t)(t + 1) * kFrBlock;
+    float l[kFrBlock / 4];
+#pragma unroll
+    for (int e = 0; e < kFrBlock / 4; ++e) {
+      const int64_t i = j0 + wv + 4 * e;
+      l[e] = i < D ? chol[fr_row(D, i) + k0 + lane] : 0.0f;
+    }
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const int s = ty + 16 * a;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int64_t j = j0 + 4 * tx + b;
+        rT[4 * tx + b][s] = (s < ns && j < D) ? W[(s0 + s) * D + j] : 0.0;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < kFrBlock / 4; ++e) Ls[wv + 4 * e][lane] = (double)l[e];
+    __syncthreads();
+    for (int ii = kFrBlock - 1; ii >= 0; --ii) {
+      double lv[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) lv[b] = Ls[ii][4 * tx + b];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        if (a < ra) {
+          const double u = rT[ii][ty + 16 * a];
+#pragma unroll
+          for (int b = 0; b < 4; ++b) acc[a][b] = fma(-lv[b], u, acc[a][b]);
+        }
+      }
+    }
+    if (K < t) {
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        const int s = ty + 16 * a;
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          if (s < ns) W[(s0 + s) * D + k0 + 4 * tx + b] = acc[a][b];
+      }
+      return;
+    }
+    __syncthreads();
+  }
+  // K == t: the diagonal block.  One load per entry (the log-diagonal for lane == r), all in flight together.
+  float l[kFrBlock / 4];
+#pragma unroll
+  for (int e = 0; e < kFrBlock / 4; ++e) {
+    const int r = wv + 4 * e;
+    const int64_t j = k0 + r;
+    l[e] = (j < D && lane <= r) ? chol[lane < r ? fr_row(D, j) + k0 + lane : j] : 0.0f;
+  }
+#pragma unroll
+  for (int e = 0; e < kFrBlock / 4; ++e) Ls[wv + 4 * e][lane] = (double)l[e];
+  if (wv == lane % 4) {  // the thread that loaded row `lane` up to its diagonal: one reciprocal per lane
+    float d = 0.0f;
+#pragma unroll
+    for (int e = 0; e < kFrBlock / 4; ++e) d = lane == wv + 4 * e ? l[e] : d;
+    Ls[lane][lane] = k0 + lane < D ? 1.0 / (double)exp_cr(d) : 1.0;
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) rT[4 * tx + b][ty + 16 * a] = acc[a][b];
+  __syncthreads();
+  // a lane per draw; the triangle of a sub-block is one wavefront's, the columns to its left are shared by the four
+  for (int c = kFrBlock / kFrSub - 1; c >= 0; --c) {
+    const int c0 = c * kFrSub;
+    double r[kFrSub];
+    if (wv == 0) {
+#pragma unroll
+      for (int q = 0; q < kFrSub; ++q) r[q] = rT[c0 + q][lane];
+#pragma unroll
+      for (int q = kFrSub - 1; q >= 0; --q) {
+        r[q] = r[q] * Ls[c0 + q][c0 + q];
+#pragma unroll
+        for (int p = 0; p < q; ++p) r[p] = fma(-Ls[c0 + q][c0 + p], r[q], r[p]);
+      }
+#pragma unroll
+      for (int q = 0; q < kFrSub; ++q) rT[c0 + q][lane] = r[q];
+    }
+    __syncthreads();
+    if (c == 0) break;
+#pragma unroll
+    for (int q = 0; q < kFrSub; ++q) r[q] = rT[c0 + q][lane];
+#pragma unroll 4
+    for (int i = wv; i < c0; i += 4) {
+      double v = rT[i][lane];
+#pragma unroll
+      for (int q = kFrSub - 1; q >= 0; --q) v = fma(-Ls[c0 + q][i], r[q], v);
+      rT[i][lane] = v;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int s = ty + 16 * a;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const int64_t k = k0 + 4 * tx + b;
+      if (s < ns && k < D) W[(s0 + s) * D + k] = rT[4 * tx + b][s];
+    }
+  }
+}
+
+// Block p of the lower triangle, row-major over (I, J <= I).
+__device__ __forceinline__ void fr_block_of(int p, int* I, int* J) {
+  int i = 0;
+  while ((i + 1) * (i + 2) / 2 <= p) ++i;
+  *I = i;
+  *J = p - i * (i + 1) / 2;
+}
+
+// part[((chunk * nbt + p) * 64 + ii) * 64 + jj] = sum over the chunk's draws, in order, of w_s[I 64 + ii] eps_s[J 64 + jj]
+// with w = -U - G (STL, U in W) or -G.  Workgroup (block p = (I, J) of the triangle, chunk of `rows` draws); the eps columns of J
+// are regenerated.  Thread (tx, ty) owns rows 4 ty + a and columns 4 tx + b of the block.
+template <bool STL>
+__global__ void __launch_bounds__(kBlock)
+k_fr_outer(Key key, int64_t S, int64_t D, int64_t rows, int nbt, const float* __restrict__ G,
+           const double* __restrict__ W, double* __restrict__ part) {
+  __shared__ double wS[kFrOuterRows][kFrBlock];
+  __shared__ double eS[kFrOuterRows][kFrBlock];
+  const int tid = threadIdx.x, tx = tid % 16, ty = tid / 16, lane = tid % 64, wv = tid / 64;
+  int I, J;
+  fr_block_of((int)blockIdx.x, &I, &J);
+  const int64_t i = (int64_t)I * kFrBlock + lane, j = (int64_t)J * kFrBlock + lane;
+  const int64_t sbeg = (int64_t)blockIdx.y * rows;
+  const int64_t send = sbeg + rows < S ? sbeg + rows : S;
+  double acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+  for (int64_t st = sbeg; st < send; st += kFrOuterRows) {
+    __syncthreads();
+    for (int e = 0; e < kFrOuterRows / 4; ++e) {
+      const int r = wv + 4 * e;
+      const int64_t s = st + r;
+      double w = 0.0;
+      if (s < send && i < D) w = STL ? -W[s * D + i] - (double)G[s * D + i] : -(double)G[s * D + i];
+      wS[r][lane] = w;
+    }
+    for (int e4 = 0; e4 < kFrOuterRows / 16; ++e4) {
+      float ev[4];
+      fr_eps4<4>(key, st + wv + 16 * e4, j < D ? send : 0, D, j, ev);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) eS[wv + 16 * e4 + 4 * e][lane] = (double)ev[e];
+    }
+    __syncthreads();
+    for (int r = 0; r < kFrOuterRows; ++r) {
+      double w[4], ev[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) w[a] = wS[r][4 * ty + a];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) ev[b] = eS[r][4 * tx + b];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[a][b] = fma(w[a], ev[b], acc[a][b]);
+    }
+  }
+  double* out = part + ((int64_t)blockIdx.y * nbt + blockIdx.x) * (kFrBlock * kFrBlock);
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) out[(4 * ty + a) * kFrBlock + 4 * tx + b] = acc[a][b];
+}
+
+// One thread per entry of a block adds the chunks in order: M_ij = sum / S, the packed entry for j < i and, on the
+// diagonal, g_chol[i] = L_ii M_ii (STL) or -1 + L_ii M_ii, rounded once.
+template <bool STL>
+__global__ void __launch_bounds__(kBlock)
+k_fr_outer_combine(int64_t S, int64_t D, int chunks, int nbt, const double* __restrict__ part,
+                   const float* __restrict__ chol, float* __restrict__ g_chol) {
+  constexpr int kPerGroup = kFrBlock * kFrBlock / kBlock;  // workgroups per block of the triangle
+  const int p = blockIdx.x / kPerGroup;
+  const int e = (blockIdx.x % kPerGroup) * kBlock + threadIdx.x;
+  int I, J;
+  fr_block_of(p, &I, &J);
+  const int64_t i = (int64_t)I * kFrBlock + e / kFrBlock, j = (int64_t)J * kFrBlock + e % kFrBlock;
+  if (i >= D || j > i) return;
+  double m = 0.0;
+  for (int c = 0; c < chunks; ++c) m += part[((int64_t)c * nbt + p) * (kFrBlock * kFrBlock) + e];
+  m /= (double)S;
+  if (j < i) {
+    g_chol[fr_row(D, i) + j] = (float)m;
+  } else {
+    const double lm = (double)exp_cr(chol[i]) * m;
+    g_chol[i] = (float)(STL ? lm : -1.0 + lm);
+  }
+}
+
+// The column sums of w (for g_mu) and of eps^2 (for the KL estimate) in the mapping of k_vi_grad_tile:
+// part[(tile * D + j) * 2 + {0, 1}].
+template <bool STL>
+__global__ void __launch_bounds__(kBlock)
+k_fr_cols_tile(Key key, int64_t S, int64_t D, int cw, const float* __restrict__ G, const double* __restrict__ W,
+               double* __restrict__ part) {
+  __shared__ double sh[kBlock];
+  const int tx = threadIdx.x % cw, ty = threadIdx.x / cw, groups = kBlock / cw;
+  const int64_t j = (int64_t)blockIdx.y * cw + tx;
+  const int64_t r0 = (int64_t)blockIdx.x * kViTile;
+  const int64_t r1 = r0 + kViTile < S ? r0 + kViTile : S;
+  double a_w = 0.0, a_e2 = 0.0;
+  if (j < D) {
+    for (int64_t r = r0 + ty; r < r1; r += groups) {
+      const double e = fr_eps(key, r, D, j);
+      a_w += STL ? -W[r * D + j] - (double)G[r * D + j] : -(double)G[r * D + j];
+      a_e2 += e * e;
+    }
+  }
+  a_w = column_total(a_w, sh, cw);
+  a_e2 = column_total(a_e2, sh, cw);
+  if (ty == 0 && j < D) {
+    double* p = part + ((int64_t)blockIdx.x * D + j) * 2;
+    p[0] = a_w;
+    p[1] = a_e2;
+  }
+}
+
+// One thread per column adds the tiles in order: g_mu = sum / S.  colsum as k_vi_grad_combine writes it, the
+// log-diagonal chol[:D] in the place of rho, for k_vi_kl.
+__global__ void __launch_bounds__(kBlock)
+k_fr_cols_combine(int64_t S, int64_t D, int64_t tiles, const double* __restrict__ part,
+                  const float* __restrict__ chol, float* __restrict__ g_mu, double* __restrict__ colsum) {
+  __shared__ double sh[kWavesPerBlock];
+  const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  double s_w = 0.0, s_e2 = 0.0, r = 0.0;
+  if (j < D) {
+    for (int64_t t = 0; t < tiles; ++t) {
+      const double* p = part + (t * D + j) * 2;
+      s_w += p[0];
+      s_e2 += p[1];
+    }
+    r = (double)chol[j];
+    g_mu[j] = (float)(s_w / (double)S);
+  }
+  s_e2 = block_sum<kWavesPerBlock>(s_e2, sh);
+  r = block_sum<kWavesPerBlock>(r, sh);
+  if (threadIdx.x == 0) {
+    colsum[2 * blockIdx.x] = s_e2;
+    colsum[2 * blockIdx.x + 1] = r;
+  }
+}
+
+bool fr_sizes_ok(int64_t S, int64_t D) {
+  return S >= 1 && S <= kFrMaxDraws && D >= 1 && D <= kFrMaxCols && S * D <= kFrMaxElems;
+}
+int64_t fr_blocks(int64_t D) { return (D + kFrBlock - 1) / kFrBlock; }
+int64_t fr_tri_blocks(int64_t D) { return fr_blocks(D) * (fr_blocks(D) + 1) / 2; }
+// Draws per chunk of the outer product, a multiple of its LDS fill: S is split until the launch has about
+// kFrOuterGroups workgroups, into at most kFrMaxChunks chunks.  A function of (S, D) alone.
+int64_t fr_chunk_rows(int64_t S, int64_t D) {
+  const int64_t fills = (S + kFrOuterRows - 1) / kFrOuterRows;
+  int64_t want = kFrOuterGroups / fr_tri_blocks(D);
+  want = want < 1 ? 1 : (want > kFrMaxChunks ? kFrMaxChunks : want);
+  const int64_t chunks = want < fills ? want : fills;
+  return (fills + chunks - 1) / chunks * kFrOuterRows;
+}
+int64_t fr_chunks(int64_t S, int64_t D) {
+  const int64_t rows = fr_chunk_rows(S, D);
+  return (S + rows - 1) / rows;
+}
+
 }  // namespace
 
 extern "C" {
@@ -225,6 +645,64 @@ int bjx_vi_meanfield_grad(void* stream, uint32_t key0, uint32_t key1, int64_t S,
   }
   hipLaunchKernelGGL(k_vi_kl, dim3(1), dim3(kKlBlock), 0, s, S, D, blocks, (const double*)colsum, logp, kl_out);
   return bjx_check_launch("bjx_vi_meanfield_grad");
+}
+
+int bjx_vi_fullrank_tile(void) { return kFrTile; }
+int bjx_vi_fullrank_block(void) { return kFrBlock; }
+
+int bjx_vi_fullrank_sample(void* stream, uint32_t key0, uint32_t key1, int64_t S, int64_t D, const float* mu,
+                           const float* chol, float* z_out) {
+  BJX_CHECK_ARG(fr_sizes_ok(S, D), "bjx_vi_fullrank_sample: bad sizes");
+  BJX_CHECK_ARG(mu && chol && z_out, "bjx_vi_fullrank_sample: null pointer");
+  const dim3 grid((unsigned)((S + kFrTile - 1) / kFrTile), (unsigned)fr_blocks(D));
+  hipLaunchKernelGGL(k_fr_sample, grid, dim3(kBlock), 0, (hipStream_t)stream, Key{key0, key1}, S, D, mu, chol, z_out);
+  return bjx_check_launch("bjx_vi_fullrank_sample");
+}
+
+int64_t bjx_vi_fullrank_grad_workspace_bytes(int64_t S, int64_t D) {
+  if (!fr_sizes_ok(S, D)) return 0;
+  // W, the outer product's partial blocks, the tiles' two partials per column, two sums per workgroup of the columns
+  return (S * D + fr_chunks(S, D) * fr_tri_blocks(D) * kFrBlock * kFrBlock + 2 * vi_tiles(S) * D +
+          2 * vi_col_blocks(D)) * (int64_t)sizeof(double);
+}
+
+int bjx_vi_fullrank_grad(void* stream, uint32_t key0, uint32_t key1, int64_t S, int64_t D, int32_t stl,
+                         const float* G, const float* logp, const float* chol, void* workspace, float* g_mu_out,
+                         float* g_chol_out, float* kl_out) {
+  BJX_CHECK_ARG(fr_sizes_ok(S, D) && (stl == 0 || stl == 1), "bjx_vi_fullrank_grad: bad sizes");
+  BJX_CHECK_ARG(G && logp && chol && workspace && g_mu_out && g_chol_out && kl_out,
+                "bjx_vi_fullrank_grad: null pointer");
+  const Key key{key0, key1};
+  const hipStream_t s = (hipStream_t)stream;
+  const int64_t tiles = vi_tiles(S), blocks = vi_col_blocks(D), rows = fr_chunk_rows(S, D);
+  const int chunks = (int)fr_chunks(S, D), nbt = (int)fr_tri_blocks(D);
+  const int cw = column_block(D);
+  double* W = (double*)workspace;
+  double* outer = W + S * D;
+  double* part = outer + (int64_t)chunks * nbt * kFrBlock * kFrBlock;
+  double* colsum = part + 2 * tiles * D;
+  const dim3 block(kBlock), outer_grid((unsigned)nbt, (unsigned)chunks);
+  const dim3 combine_grid((unsigned)(nbt * (kFrBlock * kFrBlock / kBlock)));
+  const dim3 tile_grid((unsigned)tiles, (unsigned)((D + cw - 1) / cw));
+  if (stl) {
+    const int nb = (int)fr_blocks(D);
+    for (int t = nb - 1; t >= 0; --t)
+      hipLaunchKernelGGL(k_fr_solve_step, dim3((unsigned)((S + kFrTile - 1) / kFrTile), (unsigned)(t + 1 < nb ? t + 1 : 1)),
+                         block, 0, s, key, S, D, t, chol, W);
+    hipLaunchKernelGGL(k_fr_outer<true>, outer_grid, block, 0, s, key, S, D, rows, nbt, G, (const double*)W, outer);
+    hipLaunchKernelGGL(k_fr_outer_combine<true>, combine_grid, block, 0, s, S, D, chunks, nbt, (const double*)outer,
+                       chol, g_chol_out);
+    hipLaunchKernelGGL(k_fr_cols_tile<true>, tile_grid, block, 0, s, key, S, D, cw, G, (const double*)W, part);
+  } else {
+    hipLaunchKernelGGL(k_fr_outer<false>, outer_grid, block, 0, s, key, S, D, rows, nbt, G, (const double*)W, outer);
+    hipLaunchKernelGGL(k_fr_outer_combine<false>, combine_grid, block, 0, s, S, D, chunks, nbt, (const double*)outer,
+                       chol, g_chol_out);
+    hipLaunchKernelGGL(k_fr_cols_tile<false>, tile_grid, block, 0, s, key, S, D, cw, G, (const double*)W, part);
+  }
+  hipLaunchKernelGGL(k_fr_cols_combine, dim3((unsigned)blocks), block, 0, s, S, D, tiles, (const double*)part, chol,
+                     g_mu_out, colsum);
+  hipLaunchKernelGGL(k_vi_kl, dim3(1), dim3(kKlBlock), 0, s, S, D, blocks, (const double*)colsum, logp, kl_out);
+  return bjx_check_launch("bjx_vi_fullrank_grad");
 }
 
 int bjx_optim_adam(void* stream, int64_t n, float b1, float b2, float one_minus_b1, float one_minus_b2, float c1,

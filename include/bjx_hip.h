@@ -891,6 +891,40 @@ int64_t bjx_vi_meanfield_grad_workspace_bytes(int64_t S, int64_t D);
 int bjx_vi_meanfield_grad(void* stream, uint32_t key0, uint32_t key1, int64_t S, int64_t D, int32_t stl,
                           const float* G, const float* logp, const float* rho, void* workspace, float* g_mu_out,
                           float* g_rho_out, float* kl_out);
+/* Full-rank variational inference (blackjax.fullrank_vi): q = N(mu, L L^T), L lower triangular and packed in
+ * chol (D (D + 1) / 2,): chol[i] = log L_ii for i < D, L_ii = exp_cr(chol[i]) (an fp32 value), and
+ * L_ij = chol[D + i (i - 1) / 2 + j] for j < i (torch.tril_indices(D, D, -1) order: a row of L is contiguous in j).
+ * eps is normal(key, (S, D)) as above.  Every sum below is an fp64 fma chain over the fp32 inputs in a fixed order
+ * that depends on (S, D) alone, rounded once to fp32; no atomics, no workgroup waits on another; two calls give
+ * identical bits.  The triangle is cut into B x B blocks, B = bjx_vi_fullrank_block(), and the draws into tiles of
+ * T = bjx_vi_fullrank_tile() rows.  1 <= S <= 2^20 ; 1 <= D <= 4096 ; S * D <= 2^27.
+ *
+ * bjx_vi_fullrank_sample:  z_out[s, i] = fp32(mu[i] + sum_{j <= i} L_ij eps_sj), j ascending.  One launch: a
+ *   workgroup owns T draws and B columns, regenerates eps a chunk of B columns at a time into LDS and skips the
+ *   chunks above the diagonal.
+ * bjx_vi_fullrank_grad:  from G (S, D) and logp (S,), with w_s = -u_s - G_s, L^T u_s = eps_s (stl = 1) or
+ *   w_s = -G_s (stl = 0), and M = (1 / S) sum_s w_s eps_s^T:
+ *     g_mu[i] = mean_s w_si ;  g_chol[D + i (i - 1) / 2 + j] = M_ij (j < i)
+ *     g_chol[i] = L_ii M_ii (stl = 1) or -1 + L_ii M_ii (stl = 0)
+ *     *kl_out = -(sum_sd eps_sd^2) / (2 S) - sum_{i < D} chol[i] - D log(2 pi) / 2 - mean_s logp[s]
+ *   Launches: (stl = 1 only) the solve, a right-looking blocked back-substitution from the last column block to the
+ *   first with one launch per column block (workgroup = T draws and one block: the update from the block solved by
+ *   the launch before, then, for the next block, u_j = r_j (1 / L_jj) with the fp64 reciprocal and r_i -= L_ji u_j
+ *   for i < j), which leaves U in fp64 in the workspace; the outer product, one workgroup per block (I, J <= I) of
+ *   the triangle and chunk of draws, w formed from U and G and the eps columns of J regenerated; its combine, which
+ *   adds the chunks in order; the column sums of w and eps^2 per tile of bjx_vi_meanfield_tile() rows, their
+ *   combine, and the scalar (the mean-field launch).  A NaN in G[s, i] reaches g_mu[i] and row i of the triangle (g_chol[i] and the entries (i, j < i))
+ *   only.  workspace: bjx_vi_fullrank_grad_workspace_bytes(S, D) bytes (0 for sizes out of range), 8-byte aligned,
+ *   contents scratch; it holds U, so it grows with 8 S D.
+ * Replaces: vi/fullrank_vi.py::sample, step (the Monte-Carlo KL estimate and its jax.value_and_grad). */
+int bjx_vi_fullrank_tile(void);
+int bjx_vi_fullrank_block(void);
+int bjx_vi_fullrank_sample(void* stream, uint32_t key0, uint32_t key1, int64_t S, int64_t D, const float* mu,
+                           const float* chol, float* z_out);
+int64_t bjx_vi_fullrank_grad_workspace_bytes(int64_t S, int64_t D);
+int bjx_vi_fullrank_grad(void* stream, uint32_t key0, uint32_t key1, int64_t S, int64_t D, int32_t stl,
+                         const float* G, const float* logp, const float* chol, void* workspace, float* g_mu_out,
+                         float* g_chol_out, float* kl_out);
 /* Element-wise optimiser updates over an (n,) tensor, out of place, mirroring blackjax_amd/optim.py operation by
  * operation in fp32 with no contraction and IEEE division and square root:
  *   adam:  m = (one_minus_b1 * g) + (b1 * mu) ;  v = (one_minus_b2 * (g * g)) + (b2 * nu) ;
