@@ -34,10 +34,10 @@ from typing import Any, Callable, NamedTuple
 import torch
 
 from .. import _lib
-from .._util import check_batch, eval_into, value_and_grad
+from .._util import check_batch
 from ..base import VIAlgorithm
 from ..random import key_words
-from .meanfield_vi import _num_samples
+from . import _common
 
 __all__ = ["FRVIState", "FRVIInfo", "init", "step", "sample", "kl_and_grad", "generate_fullrank_logdensity",
            "cholesky_factor", "as_top_level_api", "DRAW_TILE", "COL_BLOCK", "MAX_DIM"]
@@ -80,9 +80,7 @@ def _parameters(mu, chol_params, what: str = "state"):
 def init(position: torch.Tensor, optimizer) -> FRVIState:
     """blackjax/vi/fullrank_vi.py ``init``: ``mu = 0``, ``chol_params = 0`` (``L = I``), the optimiser's state for
     ``(mu, chol_params)``."""
-    position = check_batch(position, "position")
-    if position.ndim != 1 or position.shape[0] < 1:
-        raise ValueError(f"position must be (dim,), got {tuple(position.shape)}")
+    position = _common.position(position)
     D = position.shape[0]
     if D > MAX_DIM:
         raise ValueError(f"fullrank_vi: dimension {D} is out of range, at most {MAX_DIM} (include/bjx_hip.h, VI)")
@@ -107,7 +105,7 @@ def sample(rng_key, state: FRVIState, num_samples: int = 1) -> torch.Tensor:
     mu, chol = _parameters(state.mu, state.chol_params)
     k0, k1 = key_words(rng_key)
     with torch.cuda.device(mu.device):
-        return _draw(k0, k1, mu, chol, _num_samples(num_samples))
+        return _draw(k0, k1, mu, chol, _common.num_samples(num_samples))
 
 
 def kl_and_grad(rng_key, mu, chol_params, logp, grad, stl_estimator: bool = True):
@@ -116,27 +114,8 @@ def kl_and_grad(rng_key, mu, chol_params, logp, grad, stl_estimator: bool = True
     estimate ``mean_s(log q(z_s) - logp_s)`` (0-d) and its gradients with respect to ``mu`` ``(D,)`` and
     ``chol_params`` ``(D (D + 1) / 2,)``.  The draws themselves are not an argument: the kernels regenerate their
     noise from the key."""
-    mu, chol = _parameters(mu, chol_params, "parameters")
-    logp, G = check_batch(logp, "logp"), check_batch(grad, "grad")
-    D = mu.shape[0]
-    if G.ndim != 2 or G.shape[1] != D or G.shape[0] < 1 or logp.shape != G.shape[:1]:
-        raise ValueError(f"logp and grad must be (num_samples,) and (num_samples, {D}), got {tuple(logp.shape)} and "
-                         f"{tuple(G.shape)}")
-    if logp.device != mu.device or G.device != mu.device:
-        raise ValueError(f"logp and grad must be on {mu.device}, got {logp.device} and {G.device}")
-    S = G.shape[0]
-    k0, k1 = key_words(rng_key)
-    nbytes = _lib.load().bjx_vi_fullrank_grad_workspace_bytes(S, D)
-    if nbytes <= 0:
-        raise ValueError(f"fullrank_vi: {S} draws of dimension {D} are out of range (include/bjx_hip.h, VI)")
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=mu.device)
-    g_mu, g_chol = torch.empty_like(mu), torch.empty_like(chol)
-    kl = torch.empty((), dtype=torch.float32, device=mu.device)
-    with torch.cuda.device(mu.device):
-        _lib.call("bjx_vi_fullrank_grad", _lib.current_stream(), k0, k1, S, D, 1 if stl_estimator else 0,
-                  G.data_ptr(), logp.data_ptr(), chol.data_ptr(), ws.data_ptr(), g_mu.data_ptr(), g_chol.data_ptr(),
-                  kl.data_ptr())
-    return kl, g_mu, g_chol
+    return _common.kl_and_grad("fullrank_vi", "bjx_vi_fullrank_grad", _parameters, rng_key, mu, chol_params, logp, grad,
+                               stl_estimator)
 
 
 def step(rng_key, state: FRVIState, logdensity_fn: Callable, optimizer, num_samples: int = 5,
@@ -144,16 +123,8 @@ def step(rng_key, state: FRVIState, logdensity_fn: Callable, optimizer, num_samp
     """blackjax/vi/fullrank_vi.py ``step``: one stochastic gradient step on the KL estimate.
     -> ``(FRVIState, FRVIInfo)``."""
     mu, chol = _parameters(state.mu, state.chol_params)
-    S = _num_samples(num_samples)
-    k0, k1 = key_words(rng_key)
-    vg = value_and_grad(logdensity_fn)
-    with torch.cuda.device(mu.device):
-        z = _draw(k0, k1, mu, chol, S)
-        logp, G = eval_into(vg, z, torch.empty(S, dtype=torch.float32, device=mu.device), torch.empty_like(z))
-        kl, g_mu, g_chol = kl_and_grad((k0, k1), mu, chol, logp, G, stl_estimator)
-        updates, opt_state = optimizer.update((g_mu, g_chol), state.opt_state, (mu, chol))
-        u_mu, u_chol = updates
-        return FRVIState(mu + u_mu, chol + u_chol, opt_state), FRVIInfo(kl)
+    return _common.step(_draw, kl_and_grad, FRVIState, FRVIInfo, rng_key, mu, chol, state.opt_state, logdensity_fn,
+                        optimizer, num_samples, stl_estimator)
 
 
 def _unflatten_cholesky(chol_params: torch.Tensor) -> torch.Tensor:
@@ -192,14 +163,4 @@ def generate_fullrank_logdensity(mu, cov) -> Callable:
 def as_top_level_api(logdensity_fn: Callable, optimizer, num_samples: int = 100) -> VIAlgorithm:
     """blackjax/vi/fullrank_vi.py ``as_top_level_api``: ``init(position)``, ``step(rng_key, state)``,
     ``sample(rng_key, state, num_samples=1)``."""
-
-    def init_fn(position):
-        return init(position, optimizer)
-
-    def step_fn(rng_key, state):
-        return step(rng_key, state, logdensity_fn, optimizer, num_samples)
-
-    def sample_fn(rng_key, state, num_samples: int = 1):
-        return sample(rng_key, state, num_samples)
-
-    return VIAlgorithm(init_fn, step_fn, sample_fn)
+    return _common.as_top_level_api(init, step, sample, logdensity_fn, optimizer, num_samples)

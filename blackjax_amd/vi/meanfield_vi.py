@@ -30,9 +30,10 @@ from typing import Any, Callable, NamedTuple
 import torch
 
 from .. import _lib
-from .._util import check_batch, eval_into, value_and_grad
+from .._util import check_batch
 from ..base import VIAlgorithm
 from ..random import key_words
+from . import _common
 
 __all__ = ["MFVIState", "MFVIInfo", "init", "step", "sample", "kl_and_grad", "generate_meanfield_logdensity",
            "as_top_level_api", "GRAD_TILE"]
@@ -63,18 +64,9 @@ def _parameters(mu, rho, what: str = "state"):
     return mu, rho
 
 
-def _num_samples(num_samples) -> int:
-    s = int(num_samples)
-    if s < 1:
-        raise ValueError(f"num_samples must be at least 1, got {num_samples}")
-    return s
-
-
 def init(position: torch.Tensor, optimizer) -> MFVIState:
     """blackjax/vi/meanfield_vi.py ``init``: ``mu = 0``, ``rho = -2``, the optimiser's state for ``(mu, rho)``."""
-    position = check_batch(position, "position")
-    if position.ndim != 1 or position.shape[0] < 1:
-        raise ValueError(f"position must be (dim,), got {tuple(position.shape)}")
+    position = _common.position(position)
     mu = torch.zeros_like(position)
     rho = torch.full_like(position, -2.0)
     return MFVIState(mu, rho, optimizer.init((mu, rho)))
@@ -93,7 +85,7 @@ def sample(rng_key, state: MFVIState, num_samples: int = 1) -> torch.Tensor:
     mu, rho = _parameters(state.mu, state.rho)
     k0, k1 = key_words(rng_key)
     with torch.cuda.device(mu.device):
-        return _draw(k0, k1, mu, rho, _num_samples(num_samples))
+        return _draw(k0, k1, mu, rho, _common.num_samples(num_samples))
 
 
 def kl_and_grad(rng_key, mu, rho, logp, grad, stl_estimator: bool = True):
@@ -101,27 +93,8 @@ def kl_and_grad(rng_key, mu, rho, logp, grad, stl_estimator: bool = True):
     ``grad`` ``(S, D)`` at the draws ``sample`` makes from ``rng_key``, ``(kl, g_mu, g_rho)``: the Monte-Carlo
     estimate ``mean_s(log q(z_s) - logp_s)`` (0-d) and its gradients with respect to ``mu`` and ``rho`` (``(D,)``).
     The draws themselves are not an argument: the kernel regenerates their noise from the key."""
-    mu, rho = _parameters(mu, rho, "parameters")
-    logp, G = check_batch(logp, "logp"), check_batch(grad, "grad")
-    D = mu.shape[0]
-    if G.ndim != 2 or G.shape[1] != D or G.shape[0] < 1 or logp.shape != G.shape[:1]:
-        raise ValueError(f"logp and grad must be (num_samples,) and (num_samples, {D}), got {tuple(logp.shape)} and "
-                         f"{tuple(G.shape)}")
-    if logp.device != mu.device or G.device != mu.device:
-        raise ValueError(f"logp and grad must be on {mu.device}, got {logp.device} and {G.device}")
-    S = G.shape[0]
-    k0, k1 = key_words(rng_key)
-    nbytes = _lib.load().bjx_vi_meanfield_grad_workspace_bytes(S, D)
-    if nbytes <= 0:
-        raise ValueError(f"meanfield_vi: {S} draws of dimension {D} are out of range (include/bjx_hip.h, VI)")
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=mu.device)
-    g_mu, g_rho = torch.empty_like(mu), torch.empty_like(mu)
-    kl = torch.empty((), dtype=torch.float32, device=mu.device)
-    with torch.cuda.device(mu.device):
-        _lib.call("bjx_vi_meanfield_grad", _lib.current_stream(), k0, k1, S, D, 1 if stl_estimator else 0,
-                  G.data_ptr(), logp.data_ptr(), rho.data_ptr(), ws.data_ptr(), g_mu.data_ptr(), g_rho.data_ptr(),
-                  kl.data_ptr())
-    return kl, g_mu, g_rho
+    return _common.kl_and_grad("meanfield_vi", "bjx_vi_meanfield_grad", _parameters, rng_key, mu, rho, logp, grad,
+                               stl_estimator)
 
 
 def step(rng_key, state: MFVIState, logdensity_fn: Callable, optimizer, num_samples: int = 5,
@@ -129,16 +102,8 @@ def step(rng_key, state: MFVIState, logdensity_fn: Callable, optimizer, num_samp
     """blackjax/vi/meanfield_vi.py ``step``: one stochastic gradient step on the KL estimate.
     -> ``(MFVIState, MFVIInfo)``."""
     mu, rho = _parameters(state.mu, state.rho)
-    S = _num_samples(num_samples)
-    k0, k1 = key_words(rng_key)
-    vg = value_and_grad(logdensity_fn)
-    with torch.cuda.device(mu.device):
-        z = _draw(k0, k1, mu, rho, S)
-        logp, G = eval_into(vg, z, torch.empty(S, dtype=torch.float32, device=mu.device), torch.empty_like(z))
-        kl, g_mu, g_rho = kl_and_grad((k0, k1), mu, rho, logp, G, stl_estimator)
-        updates, opt_state = optimizer.update((g_mu, g_rho), state.opt_state, (mu, rho))
-        u_mu, u_rho = updates
-        return MFVIState(mu + u_mu, rho + u_rho, opt_state), MFVIInfo(kl)
+    return _common.step(_draw, kl_and_grad, MFVIState, MFVIInfo, rng_key, mu, rho, state.opt_state, logdensity_fn,
+                        optimizer, num_samples, stl_estimator)
 
 
 def generate_meanfield_logdensity(mu, rho) -> Callable:
@@ -157,14 +122,4 @@ def generate_meanfield_logdensity(mu, rho) -> Callable:
 def as_top_level_api(logdensity_fn: Callable, optimizer, num_samples: int = 100) -> VIAlgorithm:
     """blackjax/vi/meanfield_vi.py ``as_top_level_api``: ``init(position)``, ``step(rng_key, state)``,
     ``sample(rng_key, state, num_samples=1)``."""
-
-    def init_fn(position):
-        return init(position, optimizer)
-
-    def step_fn(rng_key, state):
-        return step(rng_key, state, logdensity_fn, optimizer, num_samples)
-
-    def sample_fn(rng_key, state, num_samples: int = 1):
-        return sample(rng_key, state, num_samples)
-
-    return VIAlgorithm(init_fn, step_fn, sample_fn)
+    return _common.as_top_level_api(init, step, sample, logdensity_fn, optimizer, num_samples)
